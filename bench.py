@@ -1,6 +1,6 @@
 """bench.py -- headline metric of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c4|c5]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 metric   : attack-iters/s = frame pairs x I-FGSM patch iterations per second
@@ -10,12 +10,19 @@ workload : configs[1] -- FlowNetC, 384x1280 synthetic frame pairs, batch 8 per G
 step     : ONE inner-loop iteration of attack() (main.py:546-611) over the rank's batch:
            paste -> FlowNetC forward -> loss -> data-gradient backward -> crop to [3,51,51] + sum -> clamp/update/re-paste,
            replayed as one HIP graph (N>1: two graphs around one RCCL all-gather of the 31 KB [crop | loss] rows).
-scaling  : weak (8 pairs per GPU); value = N*8*K / max-over-ranks time.
-Inputs are resident in HBM before the timed region.  The JSON line also carries
+scaling  : weak (8 pairs per GPU); value = N*8*K / max-over-ranks time; ms_per_step = time of one of the K timed steps.
+Inputs are resident in HBM before the timed region.  A plain run sets up, warms up, times the K steps and prints the line
+(its `roofline` is the whole step's executed FLOPs over the fp32 peak).
+--dump-outputs DIR writes what the last timed step computed -- the arrays a caller of attack() receives (the patch, the
+  adversarial frames, the loss) -- as DIR/<name>.npy (float32; arrays above 2^22 elements as a fixed seeded sample).
+--full (N=1) adds the side measurements, each run after the timed steps:
+  sustained    -- the same calls replayed for --sustained-seconds (a clock that sags under a long load shows);
   roofline     -- the dominant kernel (csrc/igemm.hip: the head's convolutions, float32-accurate on the bf16 matrix cores
                   with six products -> ceiling 2.5 PFLOP/s / 6 = 417 TFLOP/s fp32-equivalent) over the launches of one
                   iteration, each timed live with HIP events; under "kernels" every launch of the step's own kernels and
                   the MIOpen prefix against its own bound; under "step" the whole iteration's executed FLOPs;
+                  with the shader clock measured in the same process;
+  others       -- the other BASELINE configs and the full-frame step, measured live (c2);
   cpu_baseline -- the CPU oracle (torch-CPU convs + C correlation) on a bounded sample, rank 0, N=1.
 """
 from __future__ import annotations
@@ -458,6 +465,38 @@ def cpu_baseline_other(config):
                 sample=f"{n} {what}, torch-CPU convs + the C oracle's correlation / Resample2d / ChannelNorm, {dt:.1f} s")
 
 
+DUMP_MAX_ELEMENTS = 1 << 22      # 16 MB of float32 per array at most: the whole dump stays under 64 MB
+
+
+def step_outputs(ctx):
+    """What a caller of the timed path receives after its last step: attack() -> (adv_tgt, None, adv_ref, patch) and the last
+    loss of run() (patch configs); universal attack() -> (adv_img0, None, adv_img1, perturbation) and the loss (c5)."""
+    step = ctx["step"]
+    if hasattr(step, "delta"):
+        return {"adv_img0": step.adv0, "adv_img1": step.adv1, "perturbation": step.delta, "loss": step.loss_cur}
+    out = {"patch": step.patch, "loss": step.state[2:3], "adv_tgt": step.adv_tgt, "adv_ref": step.adv_ref}
+    if step.placed:
+        # every pair's patch rectangle in full: the only pixels of the frames the attack moves
+        o, ph, pw = step.origins.cpu().tolist(), step.ph, step.pw
+        for name in ("adv_tgt", "adv_ref"):
+            out[name + "_patch_windows"] = torch.stack([out[name][i, :, r:r + ph, c:c + pw] for i, (r, c) in enumerate(o)])
+    return out
+
+
+def dump_outputs(directory, ctx):
+    """DIR/<name>.npy in float32; an array of more than DUMP_MAX_ELEMENTS elements is replaced by the same fixed, seeded
+    sample of its flattened elements in every run (`<name>_sample.npy`, indices sorted)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    with torch.no_grad():
+        for name, t in step_outputs(ctx).items():
+            t = t.detach().float()
+            if t.numel() > DUMP_MAX_ELEMENTS:
+                idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMENTS].sort().values
+                t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+            np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -465,8 +504,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(CONFIG_WORKLOADS), default="c2",
                     help="c2 = the headline (BASELINE configs[1]); c4 / c5 = the configs BASELINE shards over 8 GPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the timed steps, also the side measurements (sustained run, per-kernel rooflines and the "
+                         "measured clock, the other configs, the full-frame step, the CPU baseline); the --no-* flags and "
+                         "--sustained-seconds trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, under 64 MB in all)")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="N=1: after the K timed steps, replay the same protocol for at least this long (0 = skip)")
+                    help="--full, N=1: after the K timed steps, replay the same protocol for at least this long (0 = skip)")
     ap.add_argument("--precondition-seconds", type=float, default=0.0,
                     help="optional: before the W warm-up steps, this long of the same attack() calls, untimed (a launch after idle runs ~8 %% "
                          "slower clocked than in a sustained stream, profiles/r4_igemm_clock.txt; off by default: W warm-up steps, then K timed ones)")
@@ -561,11 +606,13 @@ def main():
                          "the timed region would contain skipped work")
     if ctx["overflow"]() != 0.0:
         raise SystemExit("a patch window overflowed inside the timed region")
+    if opt.dump_outputs and rank == 0:             # before anything else runs the step again
+        dump_outputs(opt.dump_outputs, ctx)
 
     # a SUSTAINED figure beside the K-step one (N=1): the same calls for >= --sustained-seconds, so that a clock that sags
     # under a long load shows (the K = 20 region is ~0.1 s)
     sustained = None
-    if world == 1 and opt.sustained_seconds > 0:
+    if opt.full and world == 1 and opt.sustained_seconds > 0:
         ms_est = elapsed * 1e3 / opt.steps
         n_sus = int(-(-max(opt.sustained_seconds * 1e3 / ms_est, mc) // mc) * mc)
         torch.cuda.synchronize(device)
@@ -585,7 +632,7 @@ def main():
             "data": "synthetic",
             "config": {"workload": CONFIG_WORKLOADS[opt.config], "pairs_per_gpu": pairs, "global_pairs": world * pairs,
                        "preconditioning_s": opt.precondition_seconds,
-                       "weights": "synthetic seeded (no checkpoints offline)", "graph": not opt.no_graph},
+                       "weights": "synthetic seeded (no checkpoints offline)", "graph": not opt.no_graph, "full": opt.full},
         }
         if sustained is not None:
             line["sustained_ms_per_step"] = sustained["ms_per_step"]
@@ -617,7 +664,7 @@ def other_line(line, opt, ctx, world, ms):
                    loss="cossim", lr=2e-3, output_norm=0.02,
                    parallelism=f"dp{world}: one pair per rank, all-reduce(sum) of the [2,3,448,1024] gradient + loss (11 MiB) "
                                "before the sign")
-    if world == 1:
+    if opt.full and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_configs
         roof = bench_configs.igemm_roofline(ctx["net"])
@@ -662,7 +709,7 @@ def c2_line(line, opt, ctx, world, device, ms, mc):
         "the window and their data gradients, the cost volume and both of its adjoints, predict_flow; no vendor "
         "convolution kernel runs in an iteration" if engine_on else
         "float32 end to end on MIOpen (UFR_ENGINE=0)")
-    if world == 1:
+    if opt.full and world == 1:
         kernels, agg = kernel_rooflines(step, device, mc)
         step_line = line["roofline"]
         if agg is not None:

@@ -112,7 +112,58 @@ def gen_raft_corr():
          level0=blk.corr_pyramid[0], level3=blk.corr_pyramid[3])
 
 
-GENERATORS = {"ops": gen_ops, "raft_corr": gen_raft_corr}
+# ------------------------------------------------------------------------------------------ reference library
+REF_LIBRARY_PARAMS = [(1, 1, 5, 5, 0, 0, 1, 1, 2, 2, 1, 1), (3, 3, 3, 3, 5, 5, 2, 2, 2, 2, 2, 2),
+                      (2, 3, 4, 3, 1, 2, 1, 1, 1, 3, 1, 2)]
+
+
+def gen_ref_library():
+    """The reference's correlation.cpp behind oracle/_ref's C ABI (`make -C oracle ref`) on the operands of
+    tests/test_oracle_cpu.py::test_corr_oracle_equals_reference_library: inputs, gradients and its outputs."""
+    from oracle import oracle_ops
+    oracle_ops.build(ref=True)
+    assert oracle_ops.ref_lib() is not None, "oracle/_ref was not built"
+    g = torch.Generator().manual_seed(5)
+    arrays = {"params": np.array(REF_LIBRARY_PARAMS)}
+    for dtype, sfx in ((torch.float32, "f32"), (torch.float64, "f64")):
+        a = torch.randn(2, 7, 9, 13, dtype=dtype, generator=g)
+        b = torch.randn(2, 7, 9, 13, dtype=dtype, generator=g)
+        arrays.update({f"{sfx}_input1": a, f"{sfx}_input2": b})
+        for i, prm in enumerate(REF_LIBRARY_PARAMS):
+            out = oracle_ops.corr_forward(a, b, *prm, use_ref=True)
+            go = torch.randn(out.shape, dtype=dtype, generator=g)
+            g1, g2 = oracle_ops.corr_backward(a, b, go, *prm, use_ref=True)
+            arrays.update({f"{sfx}_{i}_output": out, f"{sfx}_{i}_grad_output": go, f"{sfx}_{i}_grad_input1": g1,
+                           f"{sfx}_{i}_grad_input2": g2})
+    save("corr_ref_library", **arrays)
+
+
+# ------------------------------------------------------------------------------------------ native-extension imports
+DROPIN_MODULES = ("spatial_correlation_sampler", "spatial_correlation_sampler_backend", "alt_cuda_corr", "resample2d_cuda",
+                  "channelnorm_cuda")
+
+
+def gen_native_imports():
+    """Which native-extension modules (and names) the reference's model files import, as data: file, module, names."""
+    import ast
+    import json
+    rows = []
+    for rel in ("models/submodules.py", "models/resample2d_package/resample2d.py", "models/channelnorm_package/channelnorm.py"):
+        with open(os.path.join(rh.REF, rel)) as f:
+            tree = ast.parse(f.read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Import):
+                rows += [dict(file=rel, module=a.name, names=[]) for a in node.names if a.name in DROPIN_MODULES]
+            elif isinstance(node, ast.ImportFrom) and node.module in DROPIN_MODULES:
+                rows.append(dict(file=rel, module=node.module, names=[a.name for a in node.names]))
+    path = os.path.join(HERE, "reference_native_imports.json")
+    with open(path, "w") as f:
+        json.dump(rows, f, indent=1)
+        f.write("\n")
+    print(f"wrote {path}")
+
+
+GENERATORS = {"ops": gen_ops, "raft_corr": gen_raft_corr, "ref_library": gen_ref_library, "native_imports": gen_native_imports}
 
 
 def main(argv):

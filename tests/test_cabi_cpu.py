@@ -175,19 +175,30 @@ def test_attack_reads_the_callers_module_global_args():
         caller.call(None, x, None, x, x, x, x, x)
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference"), reason="the reference tree is only mounted in the build container")
 def test_reference_model_files_import_the_dropin_ops_unchanged(tmp_path):
-    """The reference's own models/submodules.py, models/resample2d_package and models/channelnorm_package, imported from
-    where they lie with nothing but PYTHONPATH = dropin/ + repository root: their native-extension imports
-    (submodules.py:6, resample2d.py:1, channelnorm.py:1) resolve to the gfx950 mirrors."""
+    """The native-extension imports of the reference's models/submodules.py, models/resample2d_package and
+    models/channelnorm_package (submodules.py:6, resample2d.py:1, channelnorm.py:1; recorded from those files by
+    tests/golden/make_golden.py native_imports), placed in modules of the same paths and imported with nothing but
+    PYTHONPATH = dropin/ + repository root, resolve to the gfx950 mirrors."""
+    import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "tests", "golden", "reference_native_imports.json")) as f:
+        rows = json.load(f)
+    assert {r["file"] for r in rows} == {"models/submodules.py", "models/resample2d_package/resample2d.py",
+                                         "models/channelnorm_package/channelnorm.py"}
+    for r in rows:
+        path = tmp_path / r["file"]
+        path.parent.mkdir(parents=True, exist_ok=True)
+        stmt = f"from {r['module']} import {', '.join(r['names'])}\n" if r["names"] else f"import {r['module']}\n"
+        with open(path, "a") as f:
+            f.write(stmt)
     code = (
         "import sys, types\n"
         "sys.dont_write_bytecode = True\n"
-        "pkg = types.ModuleType('models'); pkg.__path__ = ['/root/reference/models']; sys.modules['models'] = pkg\n"   # skip models/__init__.py (imports a file that does not exist, SURVEY 8b)
+        f"pkg = types.ModuleType('models'); pkg.__path__ = [{str(tmp_path / 'models')!r}]; sys.modules['models'] = pkg\n"
         "import importlib\n"
         "sub = importlib.import_module('models.submodules')\n"
         "import understanding_flow_robustness_amd.spatial_correlation_sampler as mine\n"

@@ -1,6 +1,6 @@
 """CPU suite, part 1: the C oracle (oracle/ufr_oracle.c) is pinned against golden vectors produced by
-the reference's own CPU correlation (tests/golden/make_golden.py) and, where the reference library
-could be built (oracle/_ref), against that library directly -- bit for bit."""
+the reference's own CPU correlation (tests/golden/make_golden.py) and against the outputs of the reference
+library behind a C ABI (oracle/_ref; live too where it could be built) -- bit for bit."""
 import numpy as np
 import pytest
 import torch
@@ -52,19 +52,22 @@ def test_corr_oracle_full_size_digest(oracle):
 
 
 def test_corr_oracle_equals_reference_library(oracle):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref was not built (no /root/reference here)")
-    g = torch.Generator().manual_seed(5)
-    for dtype in (torch.float32, torch.float64):
-        a = torch.randn(2, 7, 9, 13, dtype=dtype, generator=g)
-        b = torch.randn(2, 7, 9, 13, dtype=dtype, generator=g)
-        for prm in [(1, 1, 5, 5, 0, 0, 1, 1, 2, 2, 1, 1), (3, 3, 3, 3, 5, 5, 2, 2, 2, 2, 2, 2),
-                    (2, 3, 4, 3, 1, 2, 1, 1, 1, 3, 1, 2)]:
-            o1, o2 = oracle.corr_forward(a, b, *prm), oracle.corr_forward(a, b, *prm, use_ref=True)
-            assert torch.equal(o1, o2), prm
-            go = torch.randn(o1.shape, dtype=dtype, generator=g)
-            x, y = oracle.corr_backward(a, b, go, *prm), oracle.corr_backward(a, b, go, *prm, use_ref=True)
-            assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]), prm
+    """Bit for bit against the reference library's own outputs on these operands (stored by tests/golden/make_golden.py
+    ref_library) and, where oracle/_ref was built, against that library live as well."""
+    z = load_golden("corr_ref_library")
+    live = oracle.ref_lib() is not None
+    for sfx in ("f32", "f64"):
+        a, b = t(z[f"{sfx}_input1"]), t(z[f"{sfx}_input2"])
+        for i, prm in enumerate(tuple(int(v) for v in p) for p in z["params"]):
+            o1 = oracle.corr_forward(a, b, *prm)
+            assert torch.equal(o1, t(z[f"{sfx}_{i}_output"])), (sfx, prm)
+            go = t(z[f"{sfx}_{i}_grad_output"])
+            x = oracle.corr_backward(a, b, go, *prm)
+            assert torch.equal(x[0], t(z[f"{sfx}_{i}_grad_input1"])) and torch.equal(x[1], t(z[f"{sfx}_{i}_grad_input2"])), (sfx, prm)
+            if live:
+                assert torch.equal(o1, oracle.corr_forward(a, b, *prm, use_ref=True)), (sfx, prm)
+                y = oracle.corr_backward(a, b, go, *prm, use_ref=True)
+                assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]), (sfx, prm)
 
 
 def test_correlate_wrapper_golden(oracle):

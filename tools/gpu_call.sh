@@ -5,7 +5,7 @@
 #   suite            python -m pytest tests -m gpu -q -x -rs
 #   tests:<a,b,..>   python -m pytest a b .. -q -x   (commas separate the words of a step's argument)
 #   bench[:flags]    python bench.py <flags>
-#   stats[:flags]    rocprofv3 --kernel-trace --stats of bench.py <flags> + the summaries under the same directory
+#   stats[:flags]    rocprofv3 --kernel-trace --stats of bench.py --full (CPU baseline, full-frame and other configs off) <flags> + summaries
 #   trace:<tag>,<iters>,<script>,<args>   rocprofv3 --kernel-trace of a python tool + steady-state table (tools/summarize_trace.py;
 #                    env:TRACE_MARKER=<kernel> names the last kernel of an iteration, default gate_kernel)
 #   traffic:<tag>,<iters>,<script>,<args>   two --pmc passes (FETCH_SIZE / WRITE_SIZE) + tools/pmc_step_traffic.py
@@ -31,7 +31,8 @@ for step in "$@"; do
              timeout -k 10 900 python bench.py $arg > $bj 2> $out/bench.err; rc=$?
              [ $rc -ne 0 ] && { tail -n 20 $out/bench.err; exit $rc; }
              python tools/summarize_bench.py $bj | head -n ${BENCH_LINES:-400} ;;
-    stats)   (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/stats -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-full-frame --no-other-configs $arg > $GRAFT_REPO_ROOT/$out/stats_bench.json 2> $GRAFT_REPO_ROOT/$out/stats.err); rc=$?
+    stats)   root=$(cd "$(dirname "$0")/.." && pwd)        # the repository: the profiler runs from $TMPDIR, not from the tree
+             (cd "$TMPDIR" && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$root/$out/stats" -- python "$root/bench.py" --full --no-cpu-baseline --no-full-frame --no-other-configs $arg > "$root/$out/stats_bench.json" 2> "$root/$out/stats.err"); rc=$?
              [ $rc -ne 0 ] && { tail -n 20 $out/stats.err; exit $rc; }
              f=$(find $out/stats -name "*kernel_stats.csv" | head -n 1); ft=$(find $out/stats -name "*kernel_trace.csv" | head -n 1)
              [ -n "$f" ] && python tools/summarize_stats.py $f 25 > $out/kernel_stats.md && head -n 14 $out/kernel_stats.md

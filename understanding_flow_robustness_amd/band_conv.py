@@ -143,6 +143,8 @@ class _BiasLeaky(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, slope):
         B, Cn = x.shape[0], x.shape[1]
+        if bias is None:                       # (a block without bias: the Robust FlowNetC family's deconvolutions)
+            bias = torch.zeros(Cn, dtype=x.dtype, device=x.device)
         L.check(L.lib().ufr_bias_leaky_forward(L.ptr(x), L.ptr(bias), B, Cn, x.numel() // (B * Cn), float(slope),
                                                L.stream()), "bias leaky forward")
         ctx.mark_dirty(x)
@@ -267,7 +269,7 @@ def conv_leaky(x, seq, band: Band | None = None, in_stride: int = 0, name: str |
     `band.incremental` is set, recomputes the band's columns only."""
     conv, act = seq[0], seq[1]
     frozen = not (conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad))
-    fused = (x.is_cuda and x.dtype == torch.float32 and conv.bias is not None and act.negative_slope > 0
+    fused = (x.is_cuda and x.dtype == torch.float32 and act.negative_slope > 0
              and (frozen or not torch.is_grad_enabled()))
     if not fused:
         return act(band_conv2d(x, conv, band, in_stride)) if isinstance(conv, torch.nn.Conv2d) else act(conv(x))

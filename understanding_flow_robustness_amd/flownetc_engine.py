@@ -105,6 +105,18 @@ class FlowNetCHeadEngine:
     def _conv(self, name):
         return getattr(self.net, name)[0]
 
+    def _bias(self, conv):
+        """The epilogue's bias; a layer without one (the Robust FlowNetC family's deconvolutions) gets zeros, bit-identical."""
+        if conv.bias is None:
+            return torch.zeros(conv.out_channels, dtype=torch.float32, device=self.dev)
+        return conv.bias.detach().float().contiguous()
+
+    def _stem_layers(self):
+        """[(name, Conv2d, level)] of the network's prefix chain (plane_graph.stem_stages), conv1 first; level = log2 of the
+        output stride.  The taps are the last layers of levels 2 and 3."""
+        from .plane_graph import stem_stages
+        return [(name, block[0], lvl) for lvl, stage in enumerate(stem_stages(self.net), 1) for name, block in stage]
+
     def _build_launches(self):
         net, g, B = self.net, self.grid, self.B
         plans = []      # (weights, make_launch kwargs without ws) -> sized together for one split-K workspace
@@ -128,7 +140,7 @@ class FlowNetCHeadEngine:
         fwd, bwd = {}, {}
         cw = lambda n, s, p: ig.conv_forward_weights(self._conv(n).weight, s, p)
         cb = lambda n, s, p: ig.conv_backward_weights(self._conv(n).weight, s, p)
-        bias = lambda n: self._conv(n).bias.detach().float().contiguous()
+        bias = lambda n: self._bias(self._conv(n))
         # forward chain (FlowNetC.py:142-160)
         if self.siamese:
             fwd["conv_redir"] = plan(cw("conv_redir", 1, 0), self.c3a_p, 0, g[8], g[8], out_planes=self.in31, out_chunk0=0,
@@ -220,28 +232,45 @@ class FlowNetCHeadEngine:
         return 128, 768
 
     def _build_prefix(self):
-        """Full-frame conv1-3 for both frames of every pair (models/FlowNetC.py:100-119), run once per attack() call, as two
-        chains of three igemm launches -- one per frame set -- that write where the head reads: the first frames' conv2 into
-        cat2's chunks 0-3 (the skip connection) and their conv3 into c3a_p, the second frames' conv3 into c3b_p.  (One chain
+        """Full-frame prefix for both frames of every pair (models/FlowNetC.py:100-119; the stages of Robust FlowNetC,
+        models/FlowNetC_flexible_larger_field.py:111-176), run once per attack() call, as two chains -- one per frame set -- of
+        conv1 and one igemm launch per further layer (`_stem_layers`) that write where the head reads: the first frames'
+        stage-2 output (conv2) into cat2's chunks 0-3 (the skip connection) and their stage-3 output (conv3) into c3a_p, the
+        second frames' into c3b_p.  (One chain
         over both sets needed three strided copies afterwards, 0.2 ms per call; with 256-row tiles the halves fill the same
         number of rounds: conv2 4 + 4 for 8, conv3 2 + 2 for 4.)"""
         B, dev = self.B, self.dev
         H, W = self.H, self.W
-        bias = lambda n: self._conv(n).bias.detach().float().contiguous()
-        w2 = ig.conv_forward_weights(self._conv("conv2").weight, 2, 2)
-        w3 = ig.conv_forward_weights(self._conv("conv3").weight, 2, 2)
+        layers = self._stem_layers()
         # conv2 (K = 25 taps x 2 chunks) at 2 x 8 frames: 1.35 ms on single-stage 128 x 128 tiles, 1.02-1.05 on 64 x 128 tiles
-        # (four workgroups per CU), 0.99-1.00 on the pipelined 128 x 128 kernel, 0.89-0.94 on the ping-pong kernel
-        v2 = v3 = self._pipe_variant
+        # (four workgroups per CU), 0.99-1.00 on the pipelined 128 x 128 kernel, 0.89-0.94 on the ping-pong kernel: every
+        # 128-column layer of the chain runs the `UFR_IGEMM_PIPE` form, a 64-column one (Robust FlowNetC's 64 -> 64) single-stage
+        wis = [None] + [ig.conv_forward_weights(conv.weight, conv.stride[0], conv.padding[0]) for _, conv, _ in layers[1:]]
+        # Only the taps must land where the head reads them; every other layer of a level writes one of two buffers of that
+        # level, alternating (one level-1 buffer of 8 frames at 384 x 1280 is 377 MB), shared by both chains (one stream)
+        scratch = {}
+
+        def level_buffer(lvl, slot, chunks):
+            if (lvl, slot) not in scratch:
+                scratch[(lvl, slot)] = ig.Planes(B, H >> lvl, W >> lvl, chunks, dev)
+            return scratch[(lvl, slot)]
         halves = {}
-        for h, c2_dst, c3_dst in (("a", self.cat2, self.c3a_p), ("b", ig.Planes(B, H // 4, W // 4, 4, dev), self.c3b_p)):
-            c1 = ig.Planes(B, H // 2, W // 2, 2, dev)
-            l2 = ig.make_launch(w2, c1, 0, (H // 4, W // 4), (H // 4, W // 4), out_planes=c2_dst, out_chunk0=0, bias=bias("conv2"),
-                                variant=v2)
-            l3 = ig.make_launch(w3, c2_dst, 0, (H // 8, W // 8), (H // 8, W // 8), out_planes=c3_dst, out_chunk0=0,
-                                bias=bias("conv3"), variant=v3)
-            P = dict(c1=c1, conv2=l2, conv3=l3, conv2_wi=w2, conv3_wi=w3, b1=bias("conv1"), w1=self._conv("conv1").weight.detach())
-            P.update(self._conv1_launch(B, H, W, c1))
+        for h, taps in (("a", {2: self.cat2, 3: self.c3a_p}), ("b", {3: self.c3b_p})):
+            outs = []
+            for i, (_, conv, lvl) in enumerate(layers):
+                later = sum(1 for _, _, l in layers[i + 1:] if l == lvl)        # layers of the same level after this one
+                outs.append(taps[lvl] if later == 0 and lvl in taps else level_buffer(lvl, later % 2, ig.pad32(conv.out_channels) // 32))
+            chain = []
+            for i in range(1, len(layers)):
+                name, conv, lvl = layers[i]
+                launch = ig.make_launch(wis[i], outs[i - 1], 0, (H >> lvl, W >> lvl), (H >> lvl, W >> lvl), out_planes=outs[i],
+                                        out_chunk0=0, bias=self._bias(conv), variant=self._variant_for(wis[i]))
+                chain.append((name, launch, wis[i]))
+            conv1 = layers[0][1]
+            P = dict(c1=outs[0], layers=chain, b1=self._bias(conv1), w1=conv1.weight.detach())
+            P.update({name: launch for name, launch, _ in chain})
+            P.update({name + "_wi": wi for name, _, wi in chain})
+            P.update(self._conv1_launch(B, H, W, outs[0]))
             halves[h] = P
         self._prefix = halves
 
@@ -249,14 +278,14 @@ class FlowNetCHeadEngine:
         """conv1 = Conv2d(3, 64, 7, 2, 3) + bias + LeakyReLU as an igemm launch over the packed planes of the raw frames
         (csrc/plane_layout.hip `conv1_pack_kernel`: pixel-unshuffle + two columns per chunk -> 8 taps of one chunk, the mean
         subtraction and the zero padding inside the buffer), writing conv1's planes directly."""
-        bias = self._conv("conv1").bias.detach().float().contiguous()
+        conv1 = self._stem_layers()[0][1]
+        bias = self._bias(conv1)
         if os.environ.get("UFR_CONV1_DIRECT", "1") != "0":
             # round 4: ONE kernel from the raw frames to conv1's planes (csrc/conv1_direct.hip): no packed buffer, no pack pass
-            conv1 = self._conv("conv1")
             return dict(direct=dict(wimg=ig.conv1_direct_weights(conv1.weight), bias=bias, c1=c1, n=n, hw=(H, W),
                                     gflop=2.0 * n * (H // 2) * (W // 2) * 147 * 64 / 1e9))
         packed = ig.Planes(n, H // 2 + 3, W // 2 + 2, 1, self.dev)
-        wi = ig.conv1_packed_weights(self._conv("conv1").weight)
+        wi = ig.conv1_packed_weights(conv1.weight)
         launch = ig.make_launch(wi, packed, 0, (H // 2, W // 2), (H // 2, W // 2), out_planes=c1, bias=bias, variant=2)
         return dict(packed=packed, conv1=launch, conv1_wi=wi)
 
@@ -289,8 +318,8 @@ class FlowNetCHeadEngine:
         def chain(h, frames, out):
             P = self._prefix[h]
             self._conv1(P, frames, None)
-            P["conv2"]()
-            P["conv3"]()
+            for _, launch, _ in P["layers"]:
+                launch()
             (self.c3a_p if h == "a" else self.c3b_p).to_nchw(256, 0, out=out)
         # (the two chains on two streams, so that one launch's tail is filled by the other chain's workgroups, measured no
         # faster: 5.638 against 5.620 ms in one call, gpurun r4_call5 -- the chains stay on one stream)
@@ -331,27 +360,34 @@ class FlowNetCHeadEngine:
         B2, dev = 2 * self.B, self.dev
         f32 = dict(dtype=torch.float32, device=dev)
         h2, w2, h4, w4, h8, w8 = wh // 2, ww // 2, wh // 4, ww // 4, wh // 8, ww // 8
-        c1, c2, c3 = ig.Planes(B2, h2, w2, 2, dev), ig.Planes(B2, h4, w4, 4, dev), ig.Planes(B2, h8, w8, 8, dev)
-        gz_c3, gz_c2 = ig.Planes(B2, h8, w8, 8, dev), ig.Planes(B2, h4, w4, 4, dev)
-        gz_c1, G_p = ig.Planes(B2, h2, w2, 2, dev), ig.GradSum(B2, h2 + 3, w2 + 2, 1, dev)
+        layers = self._stem_layers()
+        n = len(layers)
+        tap2 = max(i for i, (_, _, lvl) in enumerate(layers) if lvl == 2)      # the skip connection's layer (conv2)
+        # every layer's output stays (its LeakyReLU' is the mask of the data gradient that reaches it), and its gradient planes
+        acts = [ig.Planes(B2, wh >> lvl, ww >> lvl, ig.pad32(conv.out_channels) // 32, dev) for _, conv, lvl in layers]
+        gz = [ig.Planes(B2, wh >> lvl, ww >> lvl, ig.pad32(conv.out_channels) // 32, dev) for _, conv, lvl in layers]
+        G_p = ig.GradSum(B2, h2 + 3, w2 + 2, 1, dev)
         G_gw2 = ig.GradSum(B2, h4, w4, 4, dev)       # the conv2 tap's window gradient (first frames; second frames stay 0)
-        bias = lambda n: self._conv(n).bias.detach().float().contiguous()
-        plans = [
-            # (the window's forward convolutions: 64 x 128 tiles measured 1.3x faster than 128 x 128 at the same split,
-            # 0.047 vs 0.055 ms)
-            (ig.conv_forward_weights(self._conv("conv2").weight, 2, 2), c1, (h4, w4), (h4, w4),
-             dict(out_planes=c2, bias=bias("conv2"), variant=4)),
-            (ig.conv_forward_weights(self._conv("conv3").weight, 2, 2), c2, (h8, w8), (h8, w8),
-             dict(out_planes=c3, bias=bias("conv3"), variant=4)),
-            # conv3's data gradient + the skip connection's gradient, x LeakyReLU'(conv2) -> conv2's gradient planes
-            (ig.conv_backward_weights(self._conv("conv3").weight, 2, 2), gz_c3, (h8, w8), (h4, w4),
-             dict(add=G_gw2, mask=c2, out_planes=gz_c2)),
-            (ig.conv_backward_weights(self._conv("conv2").weight, 2, 2), gz_c2, (h4, w4), (h2, w2),
-             dict(out_planes=gz_c1, mask=c1)),
-            # conv1's data gradient with respect to the packed planes (the unpacking follows)
-            (ig.conv1_packed_backward_weights(self._conv("conv1").weight), gz_c1, (h2 + 3, w2 + 2), (h2 + 3, w2 + 2),
-             dict(out_f32=G_p)),
-        ]
+        grid = lambda i: (wh >> layers[i][2], ww >> layers[i][2])
+        plans, names = [], []
+        # (the window's forward convolutions: 64 x 128 tiles measured 1.3x faster than 128 x 128 at the same split,
+        # 0.047 vs 0.055 ms)
+        for i in range(1, n):
+            name, conv, _ = layers[i]
+            plans.append((ig.conv_forward_weights(conv.weight, conv.stride[0], conv.padding[0]), acts[i - 1], grid(i), grid(i),
+                          dict(out_planes=acts[i], bias=self._bias(conv), variant=4)))
+            names.append(name)
+        # data gradients, last layer first: x LeakyReLU'(the layer below) -> its gradient planes; where the conv2 tap's output
+        # is reached, the skip connection's gradient is added in the same epilogue
+        for i in range(n - 1, 0, -1):
+            name, conv, _ = layers[i]
+            kw = dict(add=G_gw2, mask=acts[i - 1], out_planes=gz[i - 1]) if i - 1 == tap2 else dict(out_planes=gz[i - 1], mask=acts[i - 1])
+            plans.append((ig.conv_backward_weights(conv.weight, conv.stride[0], conv.padding[0]), gz[i], grid(i), grid(i - 1), kw))
+            names.append(name + "_bwd")
+        # conv1's data gradient with respect to the packed planes (the unpacking follows)
+        plans.append((ig.conv1_packed_backward_weights(layers[0][1].weight), gz[0], (h2 + 3, w2 + 2), (h2 + 3, w2 + 2),
+                      dict(out_f32=G_p)))
+        names.append(layers[0][0] + "_bwd")
         sized = []
         for wi, x, rows, out_hw, kw in plans:
             pk = [len(t) * wi.KC for _, _, t in wi.phases]
@@ -362,12 +398,14 @@ class FlowNetCHeadEngine:
         ws = torch.empty(need, **f32)
         launches = [ig.make_launch(wi, x, 0, rows, out_hw, splitk=S, ws=ws if S > 1 else None, **kw)
                     for (wi, x, rows, out_hw, kw), S in zip(plans, sized)]
-        wis = {k + "_wi": p[0] for k, p in zip(("conv2", "conv3", "conv3_bwd", "conv2_bwd", "conv1_bwd"), plans)}
-        P = dict(**wis, hw=(wh, ww), c1=c1, c2=c2, c3=c3, gz_c3=gz_c3, gz_c2=gz_c2, G_gw2=G_gw2, ws=ws,
-                 conv2=launches[0], conv3=launches[1], conv3_bwd=launches[2], conv2_bwd=launches[3], conv1_bwd=launches[4],
+        chain = [(name, launch, p[0]) for name, launch, p in zip(names, launches, plans)]
+        P = dict(hw=(wh, ww), c1=acts[0], c2=acts[tap2], c3=acts[-1], gz_c3=gz[-1], gz_c2=gz[tap2], G_gw2=G_gw2, ws=ws,
+                 acts=acts, gz=gz, fwd=chain[:n - 1], bwd=chain[n - 1:],
                  G_p=G_p, gxw=torch.zeros(B2, 3, wh, ww, **f32),
                  c2_nchw=torch.zeros(B2, 128, h4, w4, **f32), c3_nchw=torch.zeros(B2, 256, h8, w8, **f32))
-        P.update(self._conv1_launch(B2, wh, ww, c1))
+        P.update({name: launch for name, launch, _ in chain})
+        P.update({name + "_wi": wi for name, _, wi in chain})
+        P.update(self._conv1_launch(B2, wh, ww, acts[0]))
         self._wprefixes[(wh, ww)] = P
         self._bound_wprefixes()
         return P
@@ -397,8 +435,8 @@ class FlowNetCHeadEngine:
         wh, ww = int(xw.shape[2]), int(xw.shape[3])
         P = self.window_prefix(wh, ww)
         self._conv1(P, xw.detach(), None)
-        P["conv2"]()
-        P["conv3"]()
+        for _, launch, _ in P["fwd"]:
+            launch()
         P["c2"].to_nchw(128, 0, out=P["c2_nchw"])                         # (the scatter kernels take NCHW windows)
         P["c3"].to_nchw(256, 0, out=P["c3_nchw"])
         self.scatter_window_features(P["c2_nchw"], P["c3_nchw"], win, wh, ww, m2, m3)
@@ -425,9 +463,10 @@ class FlowNetCHeadEngine:
         gz = P["gz_c3"]                          # x LeakyReLU'(conv3), split into the planes conv3's data gradient reads
         L.check(L.lib().ufr_nchw_grad_to_planes(L.ptr(gw3), L.ptr(P["c3_nchw"]), L.ptr(gz.t), gz.plane_stride, 0, 2 * B, 256, wh // 8,
                                                 ww // 8, ig.LEAKY, L.stream()), "window gradient -> planes")
-        P["conv3_bwd"]()                         # + G_gw2, x LeakyReLU'(conv2) -> gz_c2 (epilogue)
-        P["conv2_bwd"]()                         # x LeakyReLU'(conv1) -> conv1's gradient planes
-        P["conv1_bwd"]()                         # -> gradient of the packed planes -> gradient of the raw window stack
+        # layer by layer down the chain: x LeakyReLU'(the layer below) -> its gradient planes (epilogue), + G_gw2 where the conv2
+        # tap's output is reached; conv1's -> gradient of the packed planes -> gradient of the raw window stack
+        for _, launch, _ in P["bwd"]:
+            launch()
         L.check(L.lib().ufr_conv1_unpack_grad(L.ptr(P["G_p"].t), L.ptr(P["gxw"]), 2 * B, wh, ww, L.stream()), "conv1 unpack")
         return P["gxw"]
 
@@ -501,19 +540,17 @@ class FlowNetCHeadEngine:
         if self._prefix is not None:           # full-frame conv1-3 of the first / second frames, once per attack() call
             for h, suffix in (("a", ""), ("b", " 2nd frames")):
                 F = self._prefix[h]
-                for key in ("conv1", "conv2", "conv3"):
-                    if key not in F:
-                        continue
-                    d = F[key].desc
-                    rows.append((key + suffix, "fwd", "prefix", F[key], F[key + "_wi"].flops(d.B * d.Hr * d.Wr) / 1e9))
+                packed = [("conv1", F["conv1"], F["conv1_wi"])] if "conv1" in F else []    # (UFR_CONV1_DIRECT=0)
+                for key, launch, wi in packed + F["layers"]:
+                    d = launch.desc
+                    rows.append((key + suffix, "fwd", "prefix", launch, wi.flops(d.B * d.Hr * d.Wr) / 1e9))
         P = getattr(self, "_wprefix", None)
-        if P is not None:                      # conv2 / conv3 of the attack's prefix window (every iteration)
-            for name, kind, key in (("conv1", "fwd", "conv1"), ("conv2", "fwd", "conv2"), ("conv3", "fwd", "conv3"),
-                                    ("conv3", "bwd", "conv3_bwd"), ("conv2", "bwd", "conv2_bwd"), ("conv1", "bwd", "conv1_bwd")):
-                if key not in P:
-                    continue
-                d = P[key].desc
-                rows.append((name, kind, "window", P[key], P[key + "_wi"].flops(d.B * d.Hr * d.Wr) / 1e9))
+        if P is not None:                      # the prefix chain on the attack's window and its data gradient (every iteration)
+            packed = [("conv1", P["conv1"], P["conv1_wi"])] if "conv1" in P else []
+            for kind, chain in (("fwd", packed + P["fwd"]), ("bwd", P["bwd"])):
+                for key, launch, wi in chain:
+                    d = launch.desc
+                    rows.append((key[:-4] if kind == "bwd" else key, kind, "window", launch, wi.flops(d.B * d.Hr * d.Wr) / 1e9))
         return rows
 
     def conv1_direct_table(self):

@@ -33,9 +33,9 @@ def _conv(cin, cout, k=3, stride=1):
     return ConvLeaky(nn.Conv2d(cin, cout, k, stride, (k - 1) // 2, bias=True), nn.LeakyReLU(0.1, inplace=True))
 
 
-def _deconv(cin, cout):
-    """submodules.py:75-82."""
-    return ConvLeaky(nn.ConvTranspose2d(cin, cout, 4, 2, 1, bias=True), nn.LeakyReLU(0.1, inplace=True))
+def _deconv(cin, cout, bias=True):
+    """submodules.py:75-82 (bias=False: FlowNetC_flexible_larger_field.py:61-66, FlowNetC_predict_bias.py)."""
+    return ConvLeaky(nn.ConvTranspose2d(cin, cout, 4, 2, 1, bias=bias), nn.LeakyReLU(0.1, inplace=True))
 
 
 def correlate(input1, input2, patch_size=21, dilation_patch=2, band=None, in_stride=8):
@@ -61,25 +61,36 @@ class FlowNetC(nn.Module):
               ("predict_flow3", 386), ("predict_flow2", 194))
     _UPS = ("upsampled_flow6_to_5", "upsampled_flow5_to_4", "upsampled_flow4_to_3", "upsampled_flow3_to_2")
 
-    def __init__(self, batchNorm=False, div_flow=20, return_feat_maps=False):
+    def __init__(self, batchNorm=False, div_flow=20, return_feat_maps=False, deconv_bias=True, up_bias=True):
+        """deconv_bias / up_bias = False: the bias-less deconvolutions and flow upsamplers of the Robust FlowNetC family
+        (flownetc_flex.py), which also builds its own stem (`_build_stem`)."""
         super().__init__()
         if batchNorm:
             raise NotImplementedError("the attack path uses the batchNorm=False checkpoints")
         self.div_flow, self.return_feat_maps = div_flow, return_feat_maps
-        for name, cin, cout, k, s in self._ENCODER:
+        self._build_stem()
+        for name, cin, cout, k, s in self._ENCODER[3:]:
             setattr(self, name, _conv(cin, cout, k, s))
         for name, cin, cout in self._DECODER:
-            setattr(self, name, _deconv(cin, cout))
+            setattr(self, name, _deconv(cin, cout, deconv_bias))
         for name, cin in self._HEADS:
             setattr(self, name, FlowHead(cin, 2, 3, 1, 1, bias=True))
         for name in self._UPS:
-            setattr(self, name, FlowUpsample(2, 2, 4, 2, 1, bias=True))
+            setattr(self, name, FlowUpsample(2, 2, 4, 2, 1, bias=up_bias))
+        self._init_weights()
+        self.register_buffer("_mean64", torch.tensor(_RGB_MEAN, dtype=torch.float64).view(1, 3, 1, 1),
+                             persistent=False)
+
+    def _build_stem(self):
+        """conv1-3 (first in the reference's construction order, so first in the state dict)."""
+        for name, cin, cout, k, s in self._ENCODER[:3]:
+            setattr(self, name, _conv(cin, cout, k, s))
+
+    def _init_weights(self):
         for m in self.modules():                       # FlowNetC.py:53-63
             if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
                 nn.init.uniform_(m.bias)
                 nn.init.xavier_uniform_(m.weight)
-        self.register_buffer("_mean64", torch.tensor(_RGB_MEAN, dtype=torch.float64).view(1, 3, 1, 1),
-                             persistent=False)
 
     def normalize_correctly(self, im):
         """FlowNetC.py:73-79,93-94: float64 mean subtraction, then back to float32."""
@@ -95,16 +106,37 @@ class FlowNetC(nn.Module):
         stem = self._native_stem(x)
         if stem is not None:
             return stem
-        c1 = self._cl("conv1", x)
-        c2 = self._cl("conv2", c1)
-        return c2, self._cl("conv3", c2)
+        return self._stem_torch(x)[1:]
+
+    def stem_stages(self):
+        """The convolutional prefix as three stages (outputs at 1/2, 1/4, 1/8) of (name, conv + bias + LeakyReLU block):
+        what the engine's prefix chains (flownetc_engine.py, plane_graph.stem_graph) run.  conv1 = Conv2d(3, 64, 7, 2, 3)."""
+        return ((("conv1", self.conv1),), (("conv2", self.conv2),), (("conv3", self.conv3),))
+
+    def stem_refusal(self):
+        """Why the native stem does not serve this network (None: it does)."""
+        return None
+
+    def _stem_torch(self, x):
+        """The stem as torch operators: the last output of each stage."""
+        outs = []
+        for stage in self.stem_stages():
+            for name, block in stage:
+                x = conv_leaky(x, block, None, 0, name)
+            outs.append(x)
+        return tuple(outs)
 
     def _native_stem(self, x):
         """conv1-3 on the hand-written kernels (plane_graph.stem_graph: forward and data gradient on the igemm) whenever the
         network is frozen and in eval mode -- the clean forward that makes the attack's target, the validation loop, the
         full-frame attack iteration -- so that no vendor convolution runs for FlowNetC at all; None = not served (training,
         other sizes, UFR_ENGINE=0)."""
+        from .. import _lib as L
         from ..plane_graph import graph_for, native_ok, run, stem_graph
+        refusal = self.stem_refusal()
+        if refusal is not None:              # (constructions outside the native stem's scope: reported, torch spelling)
+            L.engine_gate(self, x, 64, extra=L.engine_refusal(self, x, 64) or refusal)
+            return None
         if not native_ok(self, x):
             return None
         n, _, h, w = x.shape
@@ -143,9 +175,7 @@ class FlowNetC(nn.Module):
         if stem is not None:
             c1, (c2, c3) = None, stem
         else:
-            c1 = self._cl("conv1", x)
-            c2 = self._cl("conv2", c1)
-            c3 = self._cl("conv3", c2)
+            c1, c2, c3 = self._stem_torch(x)
         c2a, c3a, c3b = c2[:B], c3[:B], c3[B:]
         feats = [c1[:B], c2a, c3a, c1[B:], c2[B:], c3b] if self.return_feat_maps else None
         return self._rest(c2a, c3a, c3b, feats)
@@ -155,7 +185,7 @@ class FlowNetC(nn.Module):
         iteration)?  Same conditions as `_engine_ok`, asked before any feature exists."""
         import os
         frozen = not any(p.requires_grad for p in self.parameters())
-        return (os.environ.get("UFR_ENGINE", "1") == "1" and not self.training
+        return (os.environ.get("UFR_ENGINE", "1") == "1" and not self.training and self.stem_refusal() is None
                 and not self.return_feat_maps and frozen and torch.device(device).type == "cuda" and H % 64 == 0 and W % 64 == 0)
 
     def _engine_ok(self, c2a, feats, band):

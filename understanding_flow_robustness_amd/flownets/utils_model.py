@@ -14,7 +14,8 @@ from .flownetc import FlowNetC
 from .weights import synthetic_state_dict
 
 _IMPLEMENTED = ("FlowNetC", "PWCNet", "PWCNet_adv_ifgsm_l2_002", "RAFT", "RAFT_adv_kitti2012_ifgsm_l2_002",
-                "FlowNet2", "FlowNetS")
+                "FlowNet2", "FlowNetS", "FlowNetCFlexLarger_k3_reps3", "FlowNetCFlexLarger_k3_reps3_adv_ifgsm_l2_002",
+                "FlowNetCFlexLarger_k5_reps0")
 
 
 def get_flownet_choices():
@@ -33,6 +34,10 @@ _CHECKPOINTS = {  # utils_model.py:100-155
     "PWCNet_adv_ifgsm_l2_002": ("adv_kitti2012_pwcnet_ifgsm_l2_0.02.pth", None),
     "RAFT": ("raft-things.pth", None),
     "RAFT_adv_kitti2012_ifgsm_l2_002": ("adv_kitti2012_raft_ifgsm_l2_0.02.pth", None),
+    # utils_model.py:106-117: bare state dicts
+    "FlowNetCFlexLarger_k3_reps3": ("RobustFlowNetC.pth", None),
+    "FlowNetCFlexLarger_k3_reps3_adv_ifgsm_l2_002": ("adv_kitti2012_robustFlow_ifgsm_l2_0.02.pth", None),
+    "FlowNetCFlexLarger_k5_reps0": ("larger_field_3x3_x0_l2.pth", None),
 }
 
 
@@ -61,6 +66,15 @@ def _build(args, return_feat_maps):
     if name == "FlowNetS":
         from .flownet2 import FlowNet2S                 # models/__init__.py:2: FlowNet2S as FlowNetS
         return FlowNet2S(return_feat_maps=return_feat_maps)
+    if re.findall("^FlowNetCFlexLarger", name):
+        from .flownetc_flex import FlowNetCFlex, FlowNetCPredictBias
+        # utils_model.py:76-98, the reference's string matching as it is
+        kernel_size = 5 if re.findall("k5", name) else 3
+        number_of_reps = int(re.search("reps([0-3])", name).group(0)[4:])
+        if kernel_size == 5 and number_of_reps == 0 and "dil" not in name and "relu" not in name:
+            return FlowNetCPredictBias(return_feat_maps=return_feat_maps)
+        return FlowNetCFlex(kernel_size=kernel_size, number_of_reps=number_of_reps, dilation=1,
+                            return_feat_maps=return_feat_maps)
     raise NotImplementedError(
         f"{name!r} is in the reference registry but outside this build's hot-path scope "
         f"(implemented: {', '.join(_IMPLEMENTED)})")

@@ -119,8 +119,9 @@ class PlaneGraph:
         nch = ig.pad32(N) // 32
         wi, wib = ig.deconv_forward_weights(w, 1), ig.deconv_backward_weights(w, 1)
         gz = ig.Planes(self.B, db.H, db.W, nch, self.dev)
-        fwd = self._launch(wi, sb.planes, s0, (sb.H, sb.W), (db.H, db.W), out_planes=db.planes, out_chunk0=d0,
-                           bias=bias.detach().float().contiguous(), slope=slope)
+        # (a deconvolution without bias -- the Robust FlowNetC family's -- gets a zero bias: the same epilogue, bit for bit)
+        b = bias.detach().float().contiguous() if bias is not None else torch.zeros(N, dtype=torch.float32, device=self.dev)
+        fwd = self._launch(wi, sb.planes, s0, (sb.H, sb.W), (db.H, db.W), out_planes=db.planes, out_chunk0=d0, bias=b, slope=slope)
         bwd = self._launch(wib, gz, 0, (sb.H, sb.W), (sb.H, sb.W), add=sb.grad, add_chunk0=s0, out_f32=sb.grad, out_f32_chunk0=s0)
         self.ops.append(dict(kind="conv", fwd=fwd, bwd=bwd, gz=gz, db=db, d0=d0, nch=nch, slope=slope, wi=wi, wib=wib, sb=sb, s0=s0, sk=sk))
 
@@ -422,19 +423,36 @@ def native_ok(module, x) -> bool:
     return L.engine_gate(module, x, 64)
 
 
+def stem_stages(net):
+    """The convolutional prefix of a FlowNetC-style network as three stages of (name, Sequential(Conv2d, LeakyReLU)) whose last
+    outputs sit at 1/2, 1/4 and 1/8 of the frame: `net.stem_stages()` (FlowNetC, Robust FlowNetC), else conv1 / conv2 / conv3."""
+    if hasattr(net, "stem_stages"):
+        return net.stem_stages()
+    return ((("conv1", net.conv1),), (("conv2", net.conv2),), (("conv3", net.conv3),))
+
+
 def stem_graph(net, n, H, W, cin, dev):
-    """conv1 (7x7 / 2 over the 2x2-unshuffled input), conv2, conv3 (5x5 / 2) of FlowNetC / FlowNetS (models/FlowNetC.py:100-119,
-    models/flownet2/FlowNetS.py:15-60) -> conv2 and conv3 as NCHW tensors; `net` has conv1 / conv2 / conv3 = Sequential(Conv2d, LeakyReLU)."""
+    """The prefix of FlowNetC / FlowNetS / Robust FlowNetC (models/FlowNetC.py:100-119, models/flownet2/FlowNetS.py:15-60,
+    models/FlowNetC_flexible_larger_field.py:111-176) as a chain of stages (`stem_stages`): conv1 (7x7 / 2 over the
+    2x2-unshuffled input), then every layer on the igemm -> the last outputs of stages 2 and 3 as NCHW tensors.  Every layer
+    keeps its own buffer (the adjoint reads each LeakyReLU' mask); FlowNetC's stages have one layer each (c1, c2, c3)."""
     g = PlaneGraph(n, dev)
-    g.buffer("pin", H // 2, W // 2, (4 * cin + 31) // 32)
-    g.buffer("c1", H // 2, W // 2, 2)
-    g.buffer("c2", H // 4, W // 4, 4)
-    g.buffer("c3", H // 8, W // 8, 8)
+    pin = (4 * cin + 31) // 32
+    g.buffer("pin", H // 2, W // 2, pin)
+    layers = []
+    for s, stage in enumerate(stem_stages(net), 1):
+        for j, (_, block) in enumerate(stage):
+            name = f"c{s}" if j == len(stage) - 1 else f"c{s}_{j}"
+            g.buffer(name, H >> s, W >> s, ig.pad32(block[0].out_channels) // 32)
+            layers.append((name, block[0]))
     g.input_packed12("pin", cin)
-    c1, c2, c3 = net.conv1[0], net.conv2[0], net.conv3[0]
-    g.conv(c1.weight, c1.bias, ("pin", 0, (4 * cin + 31) // 32), ("c1", 0), taps_unshuffled=True)
-    g.conv(c2.weight, c2.bias, ("c1", 0, 2), ("c2", 0), stride=2)
-    g.conv(c3.weight, c3.bias, ("c2", 0, 4), ("c3", 0), stride=2)
+    src = ("pin", 0, pin)
+    for i, (name, conv) in enumerate(layers):
+        if i == 0:
+            g.conv(conv.weight, conv.bias, src, (name, 0), taps_unshuffled=True)
+        else:
+            g.conv(conv.weight, conv.bias, src, (name, 0), stride=conv.stride[0])
+        src = (name, 0, g.bufs[name].chunks)
     g.tensor_output("c2", 128)
     g.tensor_output("c3", 256)
     return g.build()

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define UFR_ABI_VERSION 9   /* 9: ufr_build_manifest; ufr_igemm_desc: `products` 1 / 3 are served again (RAFT's opt-in reduced precision), `fuse_reduce` (split-K summed by the last workgroup of a tile, no second launch) (round 6); 8: ufr_pwc_warp_backward_owner / _workspace_bytes, ufr_raft_normalize_pair*, ufr_raft_fmap_pyramid_* (round 5); 7: the chunk-range entries of csrc/engine_small.hip take the extents of what they walk (w_chunks / g_chunks) and refuse a range that leaves it (round 5); 6: ufr_igemm_desc gained planes_chunks / f32_first_chunk; the clock probe records 8 words (round 4); 5: ufr_igemm_desc gained out_rowmajor / out_ld; ufr_igemm_clock_probe, ufr_conv1_direct, ufr_patch_paste_placed_rect (round 4); 4: ufr_igemm_desc gained tail / tail_n0 (round 3); 3: k_order (round 2) */
+#define UFR_ABI_VERSION 9   /* 9 (still): ufr_raft_context_split_forward / _backward are NEW SYMBOLS only -- no existing entry or struct changed, so the version stays (csrc/raft_context_head.hip); 9: ufr_build_manifest; ufr_igemm_desc: `products` 1 / 3 are served again (RAFT's opt-in reduced precision), `fuse_reduce` (split-K summed by the last workgroup of a tile, no second launch) (round 6); 8: ufr_pwc_warp_backward_owner / _workspace_bytes, ufr_raft_normalize_pair*, ufr_raft_fmap_pyramid_* (round 5); 7: the chunk-range entries of csrc/engine_small.hip take the extents of what they walk (w_chunks / g_chunks) and refuse a range that leaves it (round 5); 6: ufr_igemm_desc gained planes_chunks / f32_first_chunk; the clock probe records 8 words (round 4); 5: ufr_igemm_desc gained out_rowmajor / out_ld; ufr_igemm_clock_probe, ufr_conv1_direct, ufr_patch_paste_placed_rect (round 4); 4: ufr_igemm_desc gained tail / tail_n0 (round 3); 3: k_order (round 2) */
 
 enum { UFR_F32 = 0, UFR_F64 = 1, UFR_F16 = 2 };   /* UFR_F16: the spatial correlation only (generic kernels, float32 sums) */
 enum {
@@ -425,6 +425,16 @@ int ufr_raft_fmap_pyramid_forward(const float* fmap, float* const* levels_nhwc, 
                                   ufr_stream_t stream);
 int ufr_raft_fmap_pyramid_backward(const float* const* grad_levels_nhwc, int levels, float* grad_fmap, int B, int C, int H, int W,
                                    ufr_stream_t stream);
+
+/* ---- the context head of a RAFT without a separate context network (csrc/raft_context_head.hip) ---------------------------------
+ * models/raft/raft.py:169-175 behind `cnet = conv_redir(fmap1)`: ctx [B, Ct + Cr, HW] float32 ->
+ *   net [B, Ct, HW] = tanh(ctx[:, :Ct]),  inp [B, Cr, HW] = max(ctx[:, Ct:], 0), both contiguous; one launch.
+ * _backward: g_ctx [B, Ct + Cr, HW] = [ g_net * (1 - net * net) | g_inp where inp > 0, else 0 ] from the forward's OUTPUTS; g_net and
+ * g_inp may each be NULL (= zeros); one launch.  16 bytes per lane when HW % 4 == 0 and the tensors are 16-byte aligned, one float
+ * per lane otherwise. */
+int ufr_raft_context_split_forward(const float* ctx, float* net, float* inp, int B, int Ct, int Cr, long HW, ufr_stream_t stream);
+int ufr_raft_context_split_backward(const float* net, const float* inp, const float* g_net, const float* g_inp, float* g_ctx,
+                                    int B, int Ct, int Cr, long HW, ufr_stream_t stream);
 
 /* ---- RAFT convex upsampling ------------------------------------------------------------------------
  * replaces RAFT.upsample_flow (models/raft/raft.py:111-122): flow [N,2,H,W], mask [N,576,H,W] (9 x 8 x 8 logits

@@ -151,6 +151,8 @@ SIGNATURES = {
     "ufr_raft_normalize_pair_backward": [_vp, _vp, _vp, _l, _vp],
     "ufr_raft_fmap_pyramid_forward": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ufr_raft_fmap_pyramid_backward": [_vp, _i, _vp, _i, _i, _i, _i, _vp],
+    "ufr_raft_context_split_forward": [_vp, _vp, _vp, _i, _i, _i, _l, _vp],
+    "ufr_raft_context_split_backward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp],
     "ufr_igemm": [C.POINTER(IgemmDesc), _vp],
     "ufr_flow_upscale4_forward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "ufr_flow_upscale4_backward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],

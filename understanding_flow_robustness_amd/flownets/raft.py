@@ -15,6 +15,11 @@ of the reference (so `raft-things.pth` loads unchanged).  Differences, all on pu
     accumulation -- what a bfloat16 autocast computes, 1/6 of the matrix work); `UFR_RAFT_PRECISION=bf16x3` the three leading
     products (~16 significand bits, 1/2 of the work).  `RAFT.products()` says which form a forward will take.  The torch
     fallback path (training mode, parameters that want gradients) ignores the switch and stays float32.
+
+`args.flowNetCEnc and args.no_separate_context` (registry name RAFT_FlowNetCEncoder_WoContext, raft.py:55-62, extractor.py:292-391): the
+same update block behind FlowNetC's three-layer stem, `conv_redir` (1x1) of frame 1's feature map in place of a context network.  Frozen,
+in eval mode, on HIP float32 tensors the stem and conv_redir are one PlaneGraph (plane_graph.stem_graph with conv_redir as its `head`) and the split into
+tanh / relu halves one kernel each way (raft_glue.context_split, csrc/raft_context_head.hip); everything behind is the code above.
 """
 from __future__ import annotations
 
@@ -103,6 +108,36 @@ class BasicEncoder(nn.Module):
             return torch.split(x, [n, n], dim=0) if pair else x
         x = self.relu1(self.norm1(self.conv1(x)))
         x = self.conv2(self.layer3(self.layer2(self.layer1(x))))
+        if self.training and self.dropout is not None:
+            x = self.dropout(x)
+        return torch.split(x, [n, n], dim=0) if pair else x
+
+
+class FlowNetCEncoder(nn.Module):
+    """extractor.py:292-391 with norm_fn="none": FlowNetC's stem, Conv2d(3, 64, 7, 2, 3), Conv2d(64, 128, 5, 2, 2),
+    Conv2d(128, output_dim, 5, 2, 2), each with bias and LeakyReLU(0.1) (state-dict keys conv1.0.weight, ...)."""
+
+    def __init__(self, output_dim=128, norm_fn="none", dropout=0.0):
+        super().__init__()
+        if norm_fn != "none":
+            raise NotImplementedError(f"FlowNetCEncoder: norm_fn {norm_fn!r} is not served (the reference's registry builds \"none\" only)")
+        self.norm_fn = norm_fn
+        for name, cin, cout, k in (("conv1", 3, 64, 7), ("conv2", 64, 128, 5), ("conv3", 128, output_dim, 5)):
+            setattr(self, name, nn.Sequential(nn.Conv2d(cin, cout, k, stride=2, padding=(k - 1) // 2, bias=True),
+                                              nn.LeakyReLU(0.1, inplace=True)))
+        self.dropout = nn.Dropout2d(p=dropout) if dropout > 0 else None
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+
+    def forward(self, x, stacked=None):
+        """The reference's torch spelling (`stacked`: the pair already concatenated along the batch, as in BasicEncoder.forward).
+        The native form of this encoder is RAFT's graph of stem + conv_redir (`RAFT._context_stem`), which also reports a refusal."""
+        pair = isinstance(x, (tuple, list))
+        if pair:
+            n = x[0].shape[0]
+            x = stacked if stacked is not None else torch.cat(x, dim=0)
+        x = self.conv3(self.conv2(self.conv1(x)))
         if self.training and self.dropout is not None:
             x = self.dropout(x)
         return torch.split(x, [n, n], dim=0) if pair else x
@@ -287,8 +322,11 @@ class RAFT(nn.Module):
         super().__init__()
         if return_feat_maps:
             raise NotImplementedError("feature-map capture is analysis-only (out of scope)")
-        if getattr(args, "small", False) or getattr(args, "flowNetCEnc", False) or getattr(args, "no_separate_context", False):
-            raise NotImplementedError("only the raft-things configuration (BasicEncoder x2) is in scope")
+        fnc, wo_context = bool(getattr(args, "flowNetCEnc", False)), bool(getattr(args, "no_separate_context", False))
+        if getattr(args, "small", False) or fnc != wo_context:
+            raise NotImplementedError("served: the raft-things configuration (BasicEncoder x2: RAFT, RAFT_adv_kitti2012_ifgsm_l2_002) and "
+                                      "flowNetCEnc with no_separate_context (RAFT_FlowNetCEncoder_WoContext); not RAFT-small, not "
+                                      "flowNetCEnc with a separate context network, not no_separate_context behind the BasicEncoder")
         self.args = args
         self.hidden_dim = self.context_dim = 128
         args.corr_radius = 4                                           # raft.py:43-52 inject defaults
@@ -296,8 +334,12 @@ class RAFT(nn.Module):
                      ("corr_levels", 4), ("iters", 12), ("fnorm", "instance"), ("cnorm", "batch")):
             if not hasattr(args, k):
                 setattr(args, k, v)
-        self.fnet = BasicEncoder(output_dim=256, norm_fn=args.fnorm, dropout=args.dropout)
-        self.cnet = BasicEncoder(output_dim=256, norm_fn=args.cnorm, dropout=args.dropout)
+        if fnc:                                                         # raft.py:55-62 (this creation order: fetch_model's positional fallback)
+            self.fnet = FlowNetCEncoder(output_dim=256, norm_fn="none", dropout=args.dropout)
+            self.conv_redir = nn.Conv2d(256, self.hidden_dim + self.context_dim, kernel_size=1, stride=1, padding=0, bias=True)
+        else:
+            self.fnet = BasicEncoder(output_dim=256, norm_fn=args.fnorm, dropout=args.dropout)
+            self.cnet = BasicEncoder(output_dim=256, norm_fn=args.cnorm, dropout=args.dropout)
         self.update_block = BasicUpdateBlock(args, hidden_dim=128)
 
     def products(self) -> int:
@@ -348,6 +390,9 @@ class RAFT(nn.Module):
         from .. import igemm as _ig
         prec = _ig.products(self.products())      # the engines built / looked up inside take this many products (6 = float32-accurate)
 
+        if not hasattr(self, "cnet"):
+            return self._forward_wo_context(image1, image2, stack, prec, flow_init, test_mode)
+
         def context():
             with prec:
                 net, inp = torch.split(self.cnet(image1), [128, 128], dim=1)
@@ -377,6 +422,55 @@ class RAFT(nn.Module):
         else:
             net, inp = context()
 
+        return self._refine(image1, net, inp, corr_fn, prec, flow_init, test_mode)
+
+    def _context_stem(self, x, n):
+        """FlowNetC's stem of both frames and conv_redir as ONE schedule on the igemm (plane_graph.stem_graph with `head`), forward and
+        data gradient: (fmap1, fmap2, conv_redir(fmap1)), or None when the engines do not serve this forward (unfrozen parameters,
+        training mode, CPU tensors, UFR_ENGINE=0, sides that are no multiples of 8: the chain halves three times; FlowNetC's 1/64
+        level does not exist here) -- reported once (`_lib.engine_gate`); the caller then takes the torch spelling."""
+        if not L.engine_gate(self, x, 8):
+            return None
+        from .. import igemm as ig
+        from ..plane_graph import graph_for, run, stem_graph
+        b, _, h, w = x.shape
+        # (the launches bake the products of their arithmetic in, like the BasicEncoder's engine: the key carries them)
+        g = graph_for(self, ("context_stem", b, h, w, str(x.device), ig._PRODUCTS[-1]),
+                      lambda: stem_graph(self.fnet, b, h, w, 3, x.device, head=self.conv_redir))
+        c3, ctx = run(g, x)
+        return c3[:n], c3[n:], ctx[:n]
+
+    def context_features(self, image1, image2, stack=None):
+        """raft.py:139-148, :169-175 for flowNetCEnc + no_separate_context on normalised frames: (fmap1, fmap2, tanh half, relu half
+        of conv_redir(fmap1)).  One stream: there is no context network to run beside the encoder."""
+        n = image1.shape[0]
+        native = self._context_stem(stack if stack is not None else torch.cat([image1, image2], dim=0), n)
+        halves = None
+        if native is not None:
+            from ..raft_glue import context_split
+            fmap1, fmap2, cnet = native
+            halves = context_split(cnet, self.hidden_dim)                  # tanh | relu as one kernel, contiguous halves
+        else:
+            fmap1, fmap2 = self.fnet([image1, image2], stacked=stack)
+            cnet = self.conv_redir(fmap1)
+        if halves is None:
+            net, inp = torch.split(cnet, [self.hidden_dim, self.context_dim], dim=1)
+            halves = torch.tanh(net), torch.relu(inp)
+        return fmap1, fmap2, halves[0], halves[1]
+
+    def _forward_wo_context(self, image1, image2, stack, prec, flow_init, test_mode):
+        with prec:
+            fmap1, fmap2, net, inp = self.context_features(image1, image2, stack)
+        fmap1, fmap2 = fmap1.float().contiguous(), fmap2.float().contiguous()
+        if self.args.alternate_corr:
+            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, share_grad=True)
+        else:
+            corr_fn = CorrBlock(fmap1, fmap2, num_levels=self.args.corr_levels, radius=self.args.corr_radius)
+        return self._refine(image1, net, inp, corr_fn, prec, flow_init, test_mode)
+
+    def _refine(self, image1, net, inp, corr_fn, prec, flow_init, test_mode):
+        """raft.py:181-233: the iterations and the convex upsampling."""
+        iters = self.args.iters
         N, _, H, W = image1.shape
         if test_mode and flow_init is None and self._engine_ok(net, H, W):
             # the 12 iterations as one explicit schedule on the native engine (raft_engine.py): same operands, same result

@@ -15,7 +15,7 @@ from .weights import synthetic_state_dict
 
 _IMPLEMENTED = ("FlowNetC", "PWCNet", "PWCNet_adv_ifgsm_l2_002", "RAFT", "RAFT_adv_kitti2012_ifgsm_l2_002",
                 "FlowNet2", "FlowNetS", "FlowNetCFlexLarger_k3_reps3", "FlowNetCFlexLarger_k3_reps3_adv_ifgsm_l2_002",
-                "FlowNetCFlexLarger_k5_reps0")
+                "FlowNetCFlexLarger_k5_reps0", "RAFT_FlowNetCEncoder_WoContext")
 
 
 def get_flownet_choices():
@@ -34,6 +34,7 @@ _CHECKPOINTS = {  # utils_model.py:100-155
     "PWCNet_adv_ifgsm_l2_002": ("adv_kitti2012_pwcnet_ifgsm_l2_0.02.pth", None),
     "RAFT": ("raft-things.pth", None),
     "RAFT_adv_kitti2012_ifgsm_l2_002": ("adv_kitti2012_raft_ifgsm_l2_0.02.pth", None),
+    "RAFT_FlowNetCEncoder_WoContext": ("raft_flowNetCEnc_noSeparateContext.pth", None),      # utils_model.py:122-142
     # utils_model.py:106-117: bare state dicts
     "FlowNetCFlexLarger_k3_reps3": ("RobustFlowNetC.pth", None),
     "FlowNetCFlexLarger_k3_reps3_adv_ifgsm_l2_002": ("adv_kitti2012_robustFlow_ifgsm_l2_0.02.pth", None),
@@ -48,16 +49,16 @@ def _build(args, return_feat_maps):
     if name in ("PWCNet", "PWCNet_adv_ifgsm_l2_002"):
         from .pwcnet import PWCDCNet
         return PWCDCNet()
-    if re.findall("^RAFT", name) and "FlowNetCEncoder" not in name:
+    if re.findall("^RAFT", name):
         from .raft import RAFT
         # utils_model.py:49-69: the Namespace is mutated, callers read these fields back
         args.small = False
         args.mixed_precision = "adv" not in name
         args.alternate_corr = getattr(args, "alternate_corr", False)
         args.fnorm, args.cnorm = "instance", "batch"
-        args.no_separate_context = False
+        args.no_separate_context = "No_Separate_Context" in name or "FlowNetCEncoder_WoContext" in name
         args.corr_levels, args.iters = 4, 12
-        args.flowNetCEnc = False
+        args.flowNetCEnc = "FlowNetCEncoder" in name
         args.update_no_motion_downsampling = False      # reference bug: never set
         return RAFT(args)
     if name == "FlowNet2":

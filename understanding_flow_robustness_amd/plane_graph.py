@@ -431,11 +431,15 @@ def stem_stages(net):
     return ((("conv1", net.conv1),), (("conv2", net.conv2),), (("conv3", net.conv3),))
 
 
-def stem_graph(net, n, H, W, cin, dev):
+def stem_graph(net, n, H, W, cin, dev, head=None):
     """The prefix of FlowNetC / FlowNetS / Robust FlowNetC (models/FlowNetC.py:100-119, models/flownet2/FlowNetS.py:15-60,
     models/FlowNetC_flexible_larger_field.py:111-176) as a chain of stages (`stem_stages`): conv1 (7x7 / 2 over the
     2x2-unshuffled input), then every layer on the igemm -> the last outputs of stages 2 and 3 as NCHW tensors.  Every layer
-    keeps its own buffer (the adjoint reads each LeakyReLU' mask); FlowNetC's stages have one layer each (c1, c2, c3)."""
+    keeps its own buffer (the adjoint reads each LeakyReLU' mask); FlowNetC's stages have one layer each (c1, c2, c3).
+    `head`: a 1x1 Conv2d without activation behind stage 3 (RAFT without a context network, models/raft/raft.py:55-62, :170:
+    `conv_redir`) as one more node -- it reads the planes stage 3's epilogue leaves (no NCHW round trip, no layout pass in front
+    of it), its linear epilogue (slope 1) needs no mask and its adjoint adds into c3's gradient sum next to the other consumers'
+    share; the results are then (c3, head(c3)) instead of (c2, c3)."""
     g = PlaneGraph(n, dev)
     pin = (4 * cin + 31) // 32
     g.buffer("pin", H // 2, W // 2, pin)
@@ -453,6 +457,13 @@ def stem_graph(net, n, H, W, cin, dev):
         else:
             g.conv(conv.weight, conv.bias, src, (name, 0), stride=conv.stride[0])
         src = (name, 0, g.bufs[name].chunks)
-    g.tensor_output("c2", 128)
-    g.tensor_output("c3", 256)
+    if head is None:
+        g.tensor_output("c2", 128)
+        g.tensor_output("c3", 256)
+    else:
+        g.buffer("head", H >> 3, W >> 3, ig.pad32(head.out_channels) // 32)
+        g.conv(head.weight, head.bias, src, ("head", 0), slope=1.0)
+        last = layers[-1][1]                                  # stage 3's last convolution: what `head` reads
+        g.tensor_output("c3", last.out_channels)
+        g.tensor_output("head", head.out_channels)
     return g.build()

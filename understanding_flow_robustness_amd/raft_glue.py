@@ -6,7 +6,11 @@ autograd Functions (one kernel each way) instead of ~35 torch operators per forw
     fmap_pyramid(fmap, levels)        AlternateCorrBlock's pyramid (models/raft/corr.py:97-105, :128-129): the map permuted to NHWC and
                                       `levels - 1` average poolings of it, each permuted to NHWC
 
-Both are bit for bit the torch spelling (tests/test_raft_glue_gpu.py compares with torch.equal), so every golden of the model holds
+    context_split(ctx, Ct)            the context head of a RAFT without a separate context network (raft.py:169-175, behind conv_redir):
+                                      `net, inp = split(ctx); tanh(net); relu(inp)` as one kernel each way with contiguous results
+                                      (csrc/raft_context_head.hip); only RAFT_FlowNetCEncoder_WoContext calls it
+
+The first two are bit for bit the torch spelling (tests/test_raft_glue_gpu.py compares with torch.equal), so every golden of the model holds
 unchanged; UFR_RAFT_GLUE=0 keeps the torch operators.
 """
 from __future__ import annotations
@@ -84,3 +88,37 @@ def fmap_pyramid(fmap, levels: int):
     if not enabled(fmap) or not 1 <= levels <= 4 or min(fmap.shape[2] >> (levels - 1), fmap.shape[3] >> (levels - 1)) < 1:
         return None
     return _FmapPyramid.apply(fmap, levels)
+
+
+class _ContextSplit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cnet, Ct):
+        cnet = cnet.contiguous()
+        B, Cn, H, W = cnet.shape
+        net, inp = cnet.new_empty(B, Ct, H, W), cnet.new_empty(B, Cn - Ct, H, W)
+        with torch.cuda.device(cnet.device):
+            L.check(L.lib().ufr_raft_context_split_forward(L.ptr(cnet), L.ptr(net), L.ptr(inp), B, Ct, Cn - Ct, H * W, L.stream()), "raft context split")
+        ctx.save_for_backward(net, inp)
+        ctx.set_materialize_grads(False)             # an output nobody differentiates arrives as None: the kernel takes NULL as zeros
+        return net, inp
+
+    @staticmethod
+    def backward(ctx, g_net, g_inp):
+        net, inp = ctx.saved_tensors
+        B, Ct, H, W = net.shape
+        Cr = inp.shape[1]
+        g_net = g_net.contiguous() if g_net is not None else None
+        g_inp = g_inp.contiguous() if g_inp is not None else None
+        g_ctx = net.new_empty(B, Ct + Cr, H, W)
+        with torch.cuda.device(net.device):
+            L.check(L.lib().ufr_raft_context_split_backward(L.ptr(net), L.ptr(inp), L.ptr(g_net) if g_net is not None else None,
+                                                            L.ptr(g_inp) if g_inp is not None else None, L.ptr(g_ctx), B, Ct, Cr, H * W, L.stream()),
+                    "raft context split backward")
+        return g_ctx, None
+
+
+def context_split(ctx, Ct: int):
+    """(tanh(ctx[:, :Ct]), relu(ctx[:, Ct:])) of ctx [B,C,H,W] as two contiguous tensors; None when the kernels do not serve the tensor."""
+    if not enabled(ctx) or ctx.dim() != 4 or not 0 < Ct < ctx.shape[1] or ctx.numel() == 0:
+        return None
+    return _ContextSplit.apply(ctx, Ct)

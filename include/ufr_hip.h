@@ -657,6 +657,33 @@ typedef struct {
                                                   epilogue and leaves the counter at zero for the next launch.  NULL: the reduce kernel follows. */
 } ufr_igemm_desc;
 int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream);
+/* The WEIGHT gradient of those convolutions (csrc/igemm_wgrad.hip; an additive entry, the ABI version stays):
+ *   dw[n][c][ky][kx] (+)= sum over (b, y, x) of gy[b, n, y, x] * x[b, c, y*sy + ky - py, x*sx + kx - px], zero outside [0,Hi) x [0,Wi)
+ * from two operands in the plane layout: x = bf16 [3][chunks][B*Hi*Wi][32] (chunks [in_chunk0, in_chunk0 + ceil(C/32)) of a buffer
+ * whose planes are x_plane_stride elements apart), gy = bf16 [3][chunks][B*Ho*Wo][32] likewise; v = p0 + p1 + p2.  The six plane
+ * products of ufr_igemm in its order, float32 accumulation on the bf16 matrix cores; the reduction runs over the pixels.
+ *   dw:  float32 [N][C][kh][kw], torch's Conv2d layout with the TRUE N and C (channel padding is never written); kh * kw <= 49;
+ *   db:  optional float32 [N], db[n] (+)= sum of gy[n] over all pixels, added in a fixed order;
+ *   accumulate: 0 = write, 1 = add onto dw / db (the complete sum is formed first, then added once);
+ *   splitm: the pixel range is cut into `splitm` slices (1 .. 256), slice s leaves its raw sums in slab s of `ws` (a slab =
+ *        N*C*kh*kw floats, + N when db != NULL; ws_elems >= splitm slabs) and a second kernel adds the slabs in ascending slice
+ *        order: no float atomics, bit-reproducible.  splitm = 1 needs no workspace.  Nothing in the call allocates or synchronises;
+ *   products: 6 (the only form).
+ * ConvTranspose2d(Cin, Cout, 4, 2, 1): the same call with the operands swapped -- x = the gradient on the fine grid (C = Cout),
+ * gy = the layer's input on the coarse grid (N = Cin), stride 2, padding 1 -- gives torch's [Cin][Cout][4][4] directly.
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: null pointers, products != 6, more than 49 taps, a chunk range that
+ * leaves either planes operand (plane_stride / (pixels * 32) chunks per plane), a workspace smaller than splitm slabs. */
+typedef struct {
+  const void* x; long x_plane_stride; int in_chunk0, C;
+  const void* gy; long gy_plane_stride; int g_chunk0, N;
+  int B, Hi, Wi, Ho, Wo, kh, kw, sy, sx, py, px;
+  float* dw;
+  float* db;
+  int accumulate;
+  int splitm; float* ws; long ws_elems;
+  int products;
+} ufr_igemm_wgrad_desc;
+int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t stream);
 /* (ABI 9) Launches since load that asked for variant 8 (direct 3 x 3) or 7 (tap reuse) and ran as a plain tile form because their
  * geometry is not covered: a tuning-table entry that reached a launch it was not swept for shows here (speed only, never results). */
 int ufr_igemm_variant_fallbacks(void);

@@ -82,6 +82,20 @@ class IgemmDesc(C.Structure):
                 ("tickets", C.c_void_p)]
 
 
+UFR_IGEMM_WGRAD_MAX_TAPS = 49
+
+
+class IgemmWgradDesc(C.Structure):
+    """ufr_igemm_wgrad_desc (include/ufr_hip.h), field for field."""
+    _fields_ = [("x", C.c_void_p), ("x_plane_stride", C.c_long), ("in_chunk0", C.c_int), ("C", C.c_int),
+                ("gy", C.c_void_p), ("gy_plane_stride", C.c_long), ("g_chunk0", C.c_int), ("N", C.c_int),
+                ("B", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int),
+                ("kh", C.c_int), ("kw", C.c_int), ("sy", C.c_int), ("sx", C.c_int), ("py", C.c_int), ("px", C.c_int),
+                ("dw", C.c_void_p), ("db", C.c_void_p), ("accumulate", C.c_int),
+                ("splitm", C.c_int), ("ws", C.c_void_p), ("ws_elems", C.c_long),
+                ("products", C.c_int)]
+
+
 UFR_MAX_CONE_LAYERS = 8
 
 
@@ -154,6 +168,7 @@ SIGNATURES = {
     "ufr_raft_context_split_forward": [_vp, _vp, _vp, _i, _i, _i, _l, _vp],
     "ufr_raft_context_split_backward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp],
     "ufr_igemm": [C.POINTER(IgemmDesc), _vp],
+    "ufr_igemm_wgrad": [C.POINTER(IgemmWgradDesc), _vp],
     "ufr_flow_upscale4_forward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "ufr_flow_upscale4_backward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "ufr_fn2_stage_pack": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
@@ -347,6 +362,16 @@ class shape_probe:
         _SHAPE_PROBE[0] -= 1
 
 
+import threading
+
+# band_conv.native_training(): thread-local like `static_handoff` below (another thread's forward must not inherit it), off by default.
+_NATIVE_TRAINING = threading.local()
+
+
+def native_training_on() -> bool:
+    return getattr(_NATIVE_TRAINING, "depth", 0) > 0
+
+
 def engine_refusal(module, x, multiple: int, spatial_scale: int = 1):
     """None when the native engines serve `module` on tensor `x` (a feature map at 1/spatial_scale of the frame whose sides
     must be multiples of `multiple`), else the reason they do not."""
@@ -371,6 +396,8 @@ def engine_gate(module, x, multiple: int, spatial_scale: int = 1, extra=None) ->
     reason = extra or engine_refusal(module, x, multiple, spatial_scale)
     if reason is None:
         return True
+    if native_training_on() and (reason == "module in training mode" or reason.startswith("parameters require gradients")):
+        return False        # band_conv.native_training(): the blocks run on the igemm and its weight gradient, not on the vendor library
     if reason not in ("UFR_ENGINE=0", "not a HIP float32 tensor") and not _SHAPE_PROBE[0]:
         key = (type(module).__name__, reason)
         VENDOR_FALLBACKS[key] = VENDOR_FALLBACKS.get(key, 0) + 1

@@ -214,6 +214,124 @@ def _frozen(mod):
     return not (mod.weight.requires_grad or (mod.bias is not None and mod.bias.requires_grad))
 
 
+# ---------------------------------------------------------------------------------------------------- native training
+class native_training:
+    """`with band_conv.native_training():` -- opt-in: inside, `conv_leaky`, `flow_head` and `flow_upsample` run a block whose
+    parameters require gradients on the hand-written kernels (HIP float32 tensors, autograd on): forward and data gradient on the
+    igemm (csrc/igemm.hip), weight and bias gradient on csrc/igemm_wgrad.hip, instead of `F.conv2d` / `F.conv_transpose2d` on
+    the vendor library.  The fine-tuning half of adversarial training (training/train.py:171-222 of the reference).
+    Scope: the FlowNetC family.  `FlowNetC` is fully served (every block of its stem and head); the Robust FlowNetC family and
+    FlowNetS come along as far as their blocks go through these three helpers (square kernels up to 5 x 5, or the 7 x 7 stride-2
+    stem on three channels; stride 1 or 2; no dilation or groups; ConvTranspose2d(., ., 4, 2, 1)) -- a block outside that raises
+    NotImplementedError instead of leaving the kernels quietly.  PWC-Net, RAFT and FlowNet2 are out of scope: their training
+    mode stays on torch operators.  Thread-local and off by default; outside the context nothing changes.  Inside it
+    `_lib.engine_gate` neither warns nor counts a forward that the attack's engines decline for training mode or trainable
+    parameters.  Weights are re-split on every call (the optimiser changes them)."""
+
+    def __enter__(self):
+        L._NATIVE_TRAINING.depth = getattr(L._NATIVE_TRAINING, "depth", 0) + 1
+        return self
+
+    def __exit__(self, *exc):
+        L._NATIVE_TRAINING.depth -= 1
+
+
+def _native_trains(x, mod) -> bool:
+    return (L.native_training_on() and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled() and not _frozen(mod))
+
+
+class _NativeTrainConv(torch.autograd.Function):
+    """Conv2d / ConvTranspose2d(., ., 4, 2, 1) + bias + LeakyReLU(slope) (slope 1: no activation) with gradients for the input, the
+    weight and the bias, every convolution on the hand-written kernels."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, transposed, stride, padding, slope):
+        from . import igemm as ig
+        B, Cin, H, W = x.shape
+        dev = x.device
+        k = int(weight.shape[-1])
+        cout = int(weight.shape[1] if transposed else weight.shape[0])
+        b = bias.detach().float().contiguous() if bias is not None else torch.zeros(cout, dtype=torch.float32, device=dev)
+        if transposed:
+            Ho, Wo = 2 * H, 2 * W
+            wi = ig.deconv_forward_weights(weight, padding)
+            rows = (H, W)
+        else:
+            Ho, Wo = (H + 2 * padding - k) // stride + 1, (W + 2 * padding - k) // stride + 1
+            rows = (Ho, Wo)
+        out = ig.Planes(B, Ho, Wo, ig.pad32(cout) // 32, dev)
+        if not transposed and k * k > L.UFR_IGEMM_MAX_TAPS:
+            # the 7 x 7 stride-2 stem on three channels: eight taps over the pixel-unshuffled, column-paired planes (igemm.conv1_packed_weights)
+            packed = ig.Planes(B, H // 2 + 3, W // 2 + 2, 1, dev)
+            zero_mean = torch.zeros(3, dtype=torch.float64, device=dev)
+            L.check(L.lib().ufr_conv1_pack_planes(L.ptr(x), None, L.ptr(packed.t), packed.plane_stride, B, 0, H, W, L.ptr(zero_mean),
+                                                  L.stream()), "conv1 pack")
+            ig.make_launch(ig.conv1_packed_weights(weight), packed, 0, rows, rows, out_planes=out, bias=b, slope=slope, variant=2,
+                           products=6)()
+        else:
+            if not transposed:
+                wi = ig.conv_forward_weights(weight, stride, padding)
+            xp = ig.Planes(B, H, W, ig.pad32(Cin) // 32, dev).load_nchw(x)
+            ig.make_launch(wi, xp, 0, rows, (Ho, Wo), out_planes=out, bias=b, slope=slope, products=6)()
+        y = out.to_nchw(cout)
+        ctx.save_for_backward(x, weight, y)
+        ctx.meta = (bool(transposed), int(stride), int(padding), float(slope), bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import igemm as ig
+        x, weight, y = ctx.saved_tensors
+        transposed, stride, padding, slope, has_bias = ctx.meta
+        B, Cin, H, W = x.shape
+        _, cout, Ho, Wo = y.shape
+        k, dev = int(weight.shape[-1]), x.device
+        gy = gy.contiguous()
+        gp = ig.Planes(B, Ho, Wo, ig.pad32(cout) // 32, dev)          # gy * LeakyReLU'(out)
+        if slope != 1.0:
+            L.check(L.lib().ufr_nchw_grad_to_planes(L.ptr(gy), L.ptr(y), L.ptr(gp.t), gp.plane_stride, 0, B, cout, Ho, Wo, slope,
+                                                    L.stream()), "gradient -> planes")
+        else:
+            gp.load_nchw(gy)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            wi = ig.deconv_backward_weights(weight, padding) if transposed else ig.conv_backward_weights(weight, stride, padding)
+            gs = ig.GradSum(B, H, W, ig.pad32(Cin) // 32, dev)
+            # (a stride-2 data gradient writes the input grid in four phases from the gy grid: rows = the gy grid)
+            rows = (Ho, Wo) if (not transposed and stride == 2) else (H, W)
+            ig.make_launch(wi, gp, 0, rows, (H, W), out_f32=gs, products=6)()
+            gx = gs.to_nchw(Cin)
+        gw = gb = None
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            xp = ig.Planes(B, H, W, ig.pad32(Cin) // 32, dev).load_nchw(x)
+            gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            gb = torch.empty(cout, dtype=torch.float32, device=dev) if has_bias and ctx.needs_input_grad[2] else None
+            ig.make_wgrad_launch(xp, 0, Cin, gp, 0, cout, k, stride, padding, transposed=transposed, dw=gw, db=gb)()
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        return gx, gw, gb, None, None, None, None
+
+
+def _native_train_block(x, conv, slope: float):
+    """The block `conv` (+ bias + LeakyReLU(slope)) on `_NativeTrainConv`; geometry outside its scope is an error, not a fallback."""
+    transposed = isinstance(conv, torch.nn.ConvTranspose2d)
+    k, s, p = conv.kernel_size, conv.stride, conv.padding
+    ok = (k[0] == k[1] and s[0] == s[1] and p[0] == p[1] and conv.dilation == (1, 1) and conv.groups == 1
+          and conv.weight.dtype == torch.float32)
+    B, Cin, H, W = x.shape
+    if transposed:
+        ok = ok and (k[0], s[0], p[0]) == (4, 2, 1) and conv.output_padding == (0, 0)
+    elif ok and k[0] * k[1] > L.UFR_IGEMM_MAX_TAPS:
+        ok = (Cin, k[0], s[0], p[0]) == (3, 7, 2, 3) and H % 2 == 0 and W % 2 == 0 and not x.requires_grad
+    elif ok:
+        ok = s[0] == 1 or (s[0] == 2 and 0 <= 2 + 2 * p[0] - k[0] <= 1 and H % 2 == 0 and W % 2 == 0)
+    if not ok:
+        raise NotImplementedError(f"band_conv.native_training: {conv} on a {H} x {W} input is outside the native training path "
+                                  "(square kernels up to 5 x 5 or the 7 x 7 stride-2 stem on three channels, stride 1 or 2 on even "
+                                  "sides, no dilation or groups, ConvTranspose2d(., ., 4, 2, 1))")
+    return _NativeTrainConv.apply(x.contiguous(), conv.weight, conv.bias, transposed, s[0], p[0], float(slope))
+
+
 def flow_head(x, conv: torch.nn.Conv2d):
     """`predict_flow*` (Conv2d(Cin, 2, 3, 1, 1), models/submodules.py:85-86): one pass over x on the device when
     the parameters are frozen (or autograd is off); the module itself otherwise."""
@@ -222,6 +340,8 @@ def flow_head(x, conv: torch.nn.Conv2d):
           and conv.bias is not None and (_frozen(conv) or not torch.is_grad_enabled()))
     if ok:
         return _Conv3x3C2.apply(x.contiguous(), conv.weight, conv.bias)
+    if _native_trains(x, conv):
+        return _native_train_block(x, conv, 1.0)
     return F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
 
 
@@ -233,6 +353,8 @@ def flow_upsample(x, deconv: torch.nn.ConvTranspose2d):
           and (_frozen(deconv) or not torch.is_grad_enabled()))
     if ok:
         return _Deconv4x4C2.apply(x.contiguous(), deconv.weight, deconv.bias)
+    if _native_trains(x, deconv):
+        return _native_train_block(x, deconv, 1.0)
     return F.conv_transpose2d(x, deconv.weight, deconv.bias, deconv.stride, deconv.padding, deconv.output_padding,
                               deconv.groups, deconv.dilation)
 
@@ -271,6 +393,8 @@ def conv_leaky(x, seq, band: Band | None = None, in_stride: int = 0, name: str |
     frozen = not (conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad))
     fused = (x.is_cuda and x.dtype == torch.float32 and act.negative_slope > 0
              and (frozen or not torch.is_grad_enabled()))
+    if not fused and act.negative_slope > 0 and _native_trains(x, conv):
+        return _native_train_block(x, conv, act.negative_slope)
     if not fused:
         return act(band_conv2d(x, conv, band, in_stride)) if isinstance(conv, torch.nn.Conv2d) else act(conv(x))
     tracked = (band is not None and band.width and name in band.inc_layers and x.requires_grad

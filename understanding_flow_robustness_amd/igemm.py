@@ -532,3 +532,81 @@ def splitk_for(M: int, Npad: int, ktiles: int, phases: int = 1, target: int = 76
     while tiles * s * 2 <= target and ktiles // (s * 2) >= min_ktiles and s < 32:
         s *= 2
     return s
+
+
+# ---------------------------------------------------------------------------------------------------- weight gradient
+class WgradLaunch(Launch):
+    """One prepared `ufr_igemm_wgrad` call (csrc/igemm_wgrad.hip); a transposed layer with a bias carries a second descriptor."""
+
+    def __init__(self, descs, keep):
+        super().__init__(descs[0], keep)
+        self.descs = descs
+
+    def __call__(self):
+        for d in self.descs:
+            L.check(L.lib().ufr_igemm_wgrad(C.byref(d), L.stream()), "igemm wgrad")
+
+    def algorithmic_bytes(self) -> float:
+        """Both operands across HBM once (three bf16 planes each) plus the float32 result."""
+        d = self.desc
+        return float(6 * 32 * (d.B * d.Hi * d.Wi * (pad32(d.C) // 32) + d.B * d.Ho * d.Wo * (pad32(d.N) // 32)) + 4 * d.N * d.C * d.kh * d.kw)
+
+
+def splitm_for(M: int, N: int, Cn: int, taps: int, target: int = 1024) -> int:
+    """Slices of the pixel range of a weight-gradient launch: split until about `target` workgroups (4 per CU) exist, keeping at
+    least four K tiles of 32 pixels per slice.  A workgroup covers 128 x 64 channels of one tap (64 x 64 below 65 output channels)."""
+    nch = pad32(N) // 32
+    tiles = -(-nch // (4 if nch > 2 else 2)) * -(-pad32(Cn) // 64) * taps
+    return max(1, min(-(-target // tiles), M // 128, 256))
+
+
+def _wgrad_desc(x, in_chunk0, Cn, gy, g_chunk0, N, kernel, stride, padding, dw, db, accumulate, splitm, keep):
+    kh, kw = _pair(kernel)
+    sy, sx = _pair(stride)
+    py, px = _pair(padding)
+    if x.B != gy.B:
+        raise RuntimeError("igemm wgrad: the operands' batch sizes differ")
+    if in_chunk0 + pad32(Cn) // 32 > x.chunks or g_chunk0 + pad32(N) // 32 > gy.chunks:
+        raise RuntimeError("igemm wgrad: the reduced chunks leave an operand's buffer")
+    if kh * kw > L.UFR_IGEMM_WGRAD_MAX_TAPS:
+        raise RuntimeError("igemm wgrad: too many taps")
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() != N * Cn * kh * kw or not dw.is_cuda:
+        raise RuntimeError(f"igemm wgrad: dw must be a contiguous HIP float32 tensor of {N} x {Cn} x {kh} x {kw} elements")
+    if db is not None and (db.dtype != torch.float32 or not db.is_contiguous() or db.numel() != N or not db.is_cuda):
+        raise RuntimeError(f"igemm wgrad: db must be a contiguous HIP float32 tensor of {N} elements")
+    d = L.IgemmWgradDesc()
+    d.x, d.x_plane_stride, d.in_chunk0, d.C = x.t.data_ptr(), x.plane_stride, int(in_chunk0), int(Cn)
+    d.gy, d.gy_plane_stride, d.g_chunk0, d.N = gy.t.data_ptr(), gy.plane_stride, int(g_chunk0), int(N)
+    d.B, d.Hi, d.Wi, d.Ho, d.Wo = x.B, x.H, x.W, gy.H, gy.W
+    d.kh, d.kw, d.sy, d.sx, d.py, d.px = kh, kw, sy, sx, py, px
+    d.dw, d.db = dw.data_ptr(), (db.data_ptr() if db is not None else None)
+    d.accumulate = 1 if accumulate else 0
+    d.splitm = int(splitm) if splitm is not None else splitm_for(gy.M, N, Cn, kh * kw)
+    if d.splitm > 1:
+        slab = N * Cn * kh * kw + (N if db is not None else 0)
+        ws = torch.empty(d.splitm * slab, dtype=torch.float32, device=dw.device)
+        d.ws, d.ws_elems = ws.data_ptr(), ws.numel()
+        keep.append(ws)
+    d.products = 6               # always the float32-accurate form, whatever the `products` stack says: a weight gradient feeds an optimiser
+    return d
+
+
+def make_wgrad_launch(x: Planes, in_chunk0: int, C: int, gy: Planes, g_chunk0: int, N: int, kernel, stride, padding, *,
+                      transposed: bool = False, dw: torch.Tensor, db: torch.Tensor | None = None, accumulate: bool = False,
+                      splitm: int | None = None) -> Launch:
+    """The weight gradient of Conv2d(C, N, kernel, stride, padding) from the layer's input planes `x` (chunks [in_chunk0, ...)) and
+    the planes of its output's gradient `gy` (chunks [g_chunk0, ...)): dw [N, C, kh, kw] float32 (written, or added onto with
+    `accumulate`), db [N] = the bias gradient.  The launch owns its split workspace; `splitm` = slices of the pixel range (None: a
+    rule of thumb that fills the chip).  Results are bit-reproducible for a given `splitm`.
+    transposed=True: ConvTranspose2d(C, N, kernel, 2, padding) with `x` its input on the coarse grid and `gy` the gradient on the
+    fine grid -- the same kernel with the operands swapped (csrc/igemm_wgrad.hip), dw [C, N, kh, kw] as torch keeps it; the bias
+    gradient [N] is the `db` of a second, one-tap call whose reduced operand is the fine gradient."""
+    keep = [x, gy, dw, db]
+    if not transposed:
+        return WgradLaunch([_wgrad_desc(x, in_chunk0, C, gy, g_chunk0, N, kernel, stride, padding, dw, db, accumulate, splitm, keep)], keep)
+    descs = [_wgrad_desc(gy, g_chunk0, N, x, in_chunk0, C, kernel, stride, padding, dw, None, accumulate, splitm, keep)]
+    if db is not None:
+        scratch = torch.zeros(N, dtype=torch.float32, device=dw.device)          # dw of the one-tap call: <gy[n], gy[first channel]>, dropped
+        keep.append(scratch)
+        descs.append(_wgrad_desc(gy, g_chunk0, 1, gy, g_chunk0, N, 1, 1, 0, scratch, db, accumulate, splitm, keep))
+    return WgradLaunch(descs, keep)

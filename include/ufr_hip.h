@@ -684,6 +684,13 @@ typedef struct {
   int products;
 } ufr_igemm_wgrad_desc;
 int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t stream);
+/* The same with a dilation (an additive entry, the ABI version and the descriptor stay):
+ *   dw[n][c][ky][kx] (+)= sum over (b, y, x) of gy[b, n, y, x] * x[b, c, y*sy + ky*dy - py, x*sx + kx*dx - px], zero outside the frame
+ * -- PWC-Net's context network (dc_conv2 .. dc_conv5: dilation 2, 4, 8, 16).  A tap whose every row or column lies outside the frame
+ * is written as exact zeros.  ufr_igemm_wgrad(d, s) IS ufr_igemm_wgrad_dilated(d, 1, 1, s).  Refused (UFR_EINVAL + ufr_last_error)
+ * before any HIP call, besides everything above: dy < 1 or dx < 1, and a geometry whose last tap (Ho-1)*sy + (kh-1)*dy + 1 (columns
+ * likewise) leaves int arithmetic (2^30). */
+int ufr_igemm_wgrad_dilated(const ufr_igemm_wgrad_desc* d, int dy, int dx, ufr_stream_t stream);
 /* (ABI 9) Launches since load that asked for variant 8 (direct 3 x 3) or 7 (tap reuse) and ran as a plain tile form because their
  * geometry is not covered: a tuning-table entry that reached a launch it was not swept for shows here (speed only, never results). */
 int ufr_igemm_variant_fallbacks(void);

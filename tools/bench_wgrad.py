@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Weight-gradient kernel and native fine-tuning step of FlowNetC against the vendor library, on one box.
+"""Weight-gradient kernel and native fine-tuning step of FlowNetC (or PWC-Net) against the vendor library, on one box.
 
     timeout 900 python tools/bench_wgrad.py [--height 384 --width 1280 --pairs 1 8 --out profiles/wgrad_layers.json]
+    timeout 900 python tools/bench_wgrad.py --net pwc          (writes profiles/wgrad_layers_pwc.json)
 
-For every layer of FlowNetC at the given frame size and every pair count:
+For every layer of the network at the given frame size and every pair count:
   * `ufr_igemm_wgrad` (igemm.make_wgrad_launch, default split) against `torch.nn.grad.conv2d_weight` (transposed layers: the
     weight output of `aten.convolution_backward`) on the same seeded operands, with the two results' largest difference;
   * one fine-tuning step (training mode, every parameter trainable, forward + backward of a multi-scale loss) inside and outside
@@ -47,6 +48,30 @@ def layers(H: int, W: int, pairs: int):
     return out
 
 
+def pwc_layers(H: int, W: int, pairs: int):
+    """The same rows plus a dilation for every convolution a PWC-Net training step runs (the siamese pyramid on 2 x pairs images;
+    `deconv2` is built by the reference and never called: left out)."""
+    from understanding_flow_robustness_amd.flownets.pwcnet import PWCDCNet
+    net = PWCDCNet()
+    scale = {}
+    for lvl, (_, _, first, second, third) in enumerate(PWCDCNet._PYRAMID, start=1):
+        scale["conv" + first] = (1 << (lvl - 1), 2 * pairs)
+        scale["conv" + second] = scale["conv" + third] = (1 << lvl, 2 * pairs)
+    for lvl in (6, 5, 4, 3, 2):
+        for name in [f"conv{lvl}_{i}" for i in range(5)] + [f"predict_flow{lvl}"] + ([f"deconv{lvl}", f"upfeat{lvl}"] if lvl > 2 else []):
+            scale[name] = (1 << lvl, pairs)
+    for i in range(1, 8):
+        scale[f"dc_conv{i}"] = (4, pairs)
+    out = []
+    for name, (sc, n) in scale.items():
+        mod = getattr(net, name)
+        conv = mod[0] if isinstance(mod, torch.nn.Sequential) else mod
+        transposed = isinstance(conv, torch.nn.ConvTranspose2d)
+        out.append((name, n, conv.in_channels, conv.out_channels, H // sc, W // sc, conv.kernel_size[0], conv.stride[0], conv.padding[0],
+                    transposed, conv.dilation[0]))
+    return out
+
+
 def window_ms(fn, iters: int) -> float:
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -74,16 +99,17 @@ def compare(cands: dict, warmup: int = 3, windows: int = 5, target_ms: float = 5
 
 def bench_layer(spec) -> dict:
     from understanding_flow_robustness_amd import igemm as ig
-    name, n, cin, cout, H, W, k, s, p, transposed = spec
+    name, n, cin, cout, H, W, k, s, p, transposed = spec[:10]
+    d = spec[10] if len(spec) > 10 else 1
     g = torch.Generator(device=DEV).manual_seed(0)
-    Ho, Wo = (2 * H, 2 * W) if transposed else ((H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1)
+    Ho, Wo = (2 * H, 2 * W) if transposed else ((H + 2 * p - (k - 1) * d - 1) // s + 1, (W + 2 * p - (k - 1) * d - 1) // s + 1)
     x = torch.randn(n, cin, H, W, device=DEV, generator=g)
     gy = torch.randn(n, cout, Ho, Wo, device=DEV, generator=g)
     wshape = (cin, cout, k, k) if transposed else (cout, cin, k, k)
     xp = ig.Planes(n, H, W, ig.pad32(cin) // 32, DEV).load_nchw(x)
     gp = ig.Planes(n, Ho, Wo, ig.pad32(cout) // 32, DEV).load_nchw(gy)
     dw = torch.empty(wshape, device=DEV)
-    launch = ig.make_wgrad_launch(xp, 0, cin, gp, 0, cout, k, s, p, transposed=transposed, dw=dw)
+    launch = ig.make_wgrad_launch(xp, 0, cin, gp, 0, cout, k, s, p, transposed=transposed, dw=dw, dilation=d)
     if transposed:
         w0 = torch.empty(wshape, device=DEV)
 
@@ -91,24 +117,24 @@ def bench_layer(spec) -> dict:
             return torch.ops.aten.convolution_backward(gy, x, w0, None, (s, s), (p, p), (1, 1), True, (0, 0), 1, (False, True, False))[1]
     else:
         def vendor():
-            return torch.nn.grad.conv2d_weight(x, wshape, gy, s, p)
+            return torch.nn.grad.conv2d_weight(x, wshape, gy, s, p, d)
     launch()
     ref = vendor()
     diff = float((dw - ref).abs().max()) / float(ref.abs().max())
     t = compare({"native": launch, "vendor": vendor})
     flops = 2.0 * n * (H * W if transposed else Ho * Wo) * k * k * cin * cout
-    return dict(layer=name, images=n, cin=cin, cout=cout, h=H, w=W, kernel=k, stride=s, transposed=transposed, splitm=int(launch.desc.splitm),
+    return dict(layer=name, images=n, cin=cin, cout=cout, h=H, w=W, kernel=k, stride=s, dilation=d, transposed=transposed, splitm=int(launch.desc.splitm),
                 gflop=flops / 1e9, native=t["native"], vendor=t["vendor"], native_over_vendor=t["native"]["median_ms"] / t["vendor"]["median_ms"],
                 native_tflops=flops / t["native"]["median_ms"] / 1e9, max_rel_diff_to_vendor=diff)
 
 
-def bench_step(H: int, W: int, pairs: int) -> dict:
+def bench_step(H: int, W: int, pairs: int, flownet: str = "FlowNetC") -> dict:
     import warnings
     from argparse import Namespace
 
     from understanding_flow_robustness_amd.band_conv import native_training
     from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
-    net = fetch_model(Namespace(flownet="FlowNetC"), synthetic_seed=0).to(DEV)
+    net = fetch_model(Namespace(flownet=flownet), synthetic_seed=0).to(DEV)
     net.train()
     for q in net.parameters():
         q.requires_grad_(True)
@@ -135,15 +161,19 @@ def main():
     ap.add_argument("--height", type=int, default=384)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--pairs", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wgrad_layers.json"))
+    ap.add_argument("--net", choices=("flownetc", "pwc"), default="flownetc", help="pwc: PWC-Net's layers and step, profiles/wgrad_layers_pwc.json")
+    ap.add_argument("--out", default=None, help="default: profiles/wgrad_layers.json (--net pwc: profiles/wgrad_layers_pwc.json)")
     ap.add_argument("--no-step", action="store_true", help="kernel timings only")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "wgrad_layers_pwc.json" if a.net == "pwc" else "wgrad_layers.json")
+    layer_list, flownet = (pwc_layers, "PWCNet") if a.net == "pwc" else (layers, "FlowNetC")
     if not torch.cuda.is_available():
         raise SystemExit("bench_wgrad: needs a HIP device (there is no CPU fallback)")
-    result = dict(device=torch.cuda.get_device_name(0), height=a.height, width=a.width, layers=[], steps=[],
+    result = dict(device=torch.cuda.get_device_name(0), net=flownet, height=a.height, width=a.width, layers=[], steps=[],
                   method="device events, 3 warm-up launches, 5 alternating windows of ~50 ms (steps: ~200 ms), median / min / max in ms")
     for pairs in a.pairs:
-        for spec in layers(a.height, a.width, pairs):
+        for spec in layer_list(a.height, a.width, pairs):
             row = dict(pairs=pairs, **bench_layer(spec))
             result["layers"].append(row)
             print(f"pairs {pairs} {row['layer']:22s} native {row['native']['median_ms']:8.3f} ms  vendor {row['vendor']['median_ms']:8.3f} ms  "
@@ -154,7 +184,7 @@ def main():
         print(f"pairs {pairs} all layers: native {tot_n:.3f} ms, vendor {tot_v:.3f} ms", flush=True)
         result.setdefault("layer_totals", []).append(dict(pairs=pairs, native_ms=tot_n, vendor_ms=tot_v))
         if not a.no_step:
-            row = bench_step(a.height, a.width, pairs)
+            row = bench_step(a.height, a.width, pairs, flownet)
             result["steps"].append(row)
             print(f"pairs {pairs} fine-tuning step: native {row['native']['median_ms']:.2f} ms, vendor {row['vendor']['median_ms']:.2f} ms "
                   f"(x{row['native_over_vendor']:.2f})", flush=True)

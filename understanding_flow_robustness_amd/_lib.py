@@ -169,6 +169,7 @@ SIGNATURES = {
     "ufr_raft_context_split_backward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp],
     "ufr_igemm": [C.POINTER(IgemmDesc), _vp],
     "ufr_igemm_wgrad": [C.POINTER(IgemmWgradDesc), _vp],
+    "ufr_igemm_wgrad_dilated": [C.POINTER(IgemmWgradDesc), _i, _i, _vp],
     "ufr_flow_upscale4_forward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "ufr_flow_upscale4_backward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "ufr_fn2_stage_pack": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],

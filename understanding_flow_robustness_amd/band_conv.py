@@ -220,11 +220,15 @@ class native_training:
     parameters require gradients on the hand-written kernels (HIP float32 tensors, autograd on): forward and data gradient on the
     igemm (csrc/igemm.hip), weight and bias gradient on csrc/igemm_wgrad.hip, instead of `F.conv2d` / `F.conv_transpose2d` on
     the vendor library.  The fine-tuning half of adversarial training (training/train.py:171-222 of the reference).
-    Scope: the FlowNetC family.  `FlowNetC` is fully served (every block of its stem and head); the Robust FlowNetC family and
-    FlowNetS come along as far as their blocks go through these three helpers (square kernels up to 5 x 5, or the 7 x 7 stride-2
-    stem on three channels; stride 1 or 2; no dilation or groups; ConvTranspose2d(., ., 4, 2, 1)) -- a block outside that raises
-    NotImplementedError instead of leaving the kernels quietly.  PWC-Net, RAFT and FlowNet2 are out of scope: their training
-    mode stays on torch operators.  Thread-local and off by default; outside the context nothing changes.  Inside it
+    Scope: the FlowNetC family and PWC-Net.  `FlowNetC` is fully served (every block of its stem and head); the Robust FlowNetC
+    family and FlowNetS come along as far as their blocks go through these three helpers (square kernels up to 5 x 5, or the
+    7 x 7 stride-2 stem on three channels; stride 1 or 2; a square dilation on stride-1 layers only; no groups;
+    ConvTranspose2d(., ., 4, 2, 1) without dilation) -- a block outside that raises NotImplementedError instead of leaving the
+    kernels quietly.  `PWCDCNet` is fully served on frames whose sides are multiples of 64 (which PWC-Net needs anyway: six
+    halvings): the pyramid, the DenseNet decoder, `predict_flow*`, `deconv*`, `upfeat*` (ConvTranspose2d(Cin, 2, 4, 2, 1), a
+    `FlowUpsample`) and the context network with its dilations 2, 4, 8 and 16; its cost volume and warp have native adjoints of
+    their own.  Each block converts NCHW <-> planes on both sides.  RAFT and FlowNet2 remain out of scope: their training mode
+    stays on torch operators.  Thread-local and off by default; outside the context nothing changes.  Inside it
     `_lib.engine_gate` neither warns nor counts a forward that the attack's engines decline for training mode or trainable
     parameters.  Weights are re-split on every call (the optimiser changes them)."""
 
@@ -245,7 +249,7 @@ class _NativeTrainConv(torch.autograd.Function):
     weight and the bias, every convolution on the hand-written kernels."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, transposed, stride, padding, slope):
+    def forward(ctx, x, weight, bias, transposed, stride, padding, slope, dilation=1):
         from . import igemm as ig
         B, Cin, H, W = x.shape
         dev = x.device
@@ -257,7 +261,8 @@ class _NativeTrainConv(torch.autograd.Function):
             wi = ig.deconv_forward_weights(weight, padding)
             rows = (H, W)
         else:
-            Ho, Wo = (H + 2 * padding - k) // stride + 1, (W + 2 * padding - k) // stride + 1
+            span = (k - 1) * dilation + 1
+            Ho, Wo = (H + 2 * padding - span) // stride + 1, (W + 2 * padding - span) // stride + 1
             rows = (Ho, Wo)
         out = ig.Planes(B, Ho, Wo, ig.pad32(cout) // 32, dev)
         if not transposed and k * k > L.UFR_IGEMM_MAX_TAPS:
@@ -270,19 +275,19 @@ class _NativeTrainConv(torch.autograd.Function):
                            products=6)()
         else:
             if not transposed:
-                wi = ig.conv_forward_weights(weight, stride, padding)
+                wi = ig.conv_forward_weights(weight, stride, padding, dilation)
             xp = ig.Planes(B, H, W, ig.pad32(Cin) // 32, dev).load_nchw(x)
             ig.make_launch(wi, xp, 0, rows, (Ho, Wo), out_planes=out, bias=b, slope=slope, products=6)()
         y = out.to_nchw(cout)
         ctx.save_for_backward(x, weight, y)
-        ctx.meta = (bool(transposed), int(stride), int(padding), float(slope), bias is not None)
+        ctx.meta = (bool(transposed), int(stride), int(padding), float(slope), bias is not None, int(dilation))
         return y
 
     @staticmethod
     def backward(ctx, gy):
         from . import igemm as ig
         x, weight, y = ctx.saved_tensors
-        transposed, stride, padding, slope, has_bias = ctx.meta
+        transposed, stride, padding, slope, has_bias, dilation = ctx.meta
         B, Cin, H, W = x.shape
         _, cout, Ho, Wo = y.shape
         k, dev = int(weight.shape[-1]), x.device
@@ -295,7 +300,7 @@ class _NativeTrainConv(torch.autograd.Function):
             gp.load_nchw(gy)
         gx = None
         if ctx.needs_input_grad[0]:
-            wi = ig.deconv_backward_weights(weight, padding) if transposed else ig.conv_backward_weights(weight, stride, padding)
+            wi = ig.deconv_backward_weights(weight, padding) if transposed else ig.conv_backward_weights(weight, stride, padding, dilation)
             gs = ig.GradSum(B, H, W, ig.pad32(Cin) // 32, dev)
             # (a stride-2 data gradient writes the input grid in four phases from the gy grid: rows = the gy grid)
             rows = (Ho, Wo) if (not transposed and stride == 2) else (H, W)
@@ -306,18 +311,21 @@ class _NativeTrainConv(torch.autograd.Function):
             xp = ig.Planes(B, H, W, ig.pad32(Cin) // 32, dev).load_nchw(x)
             gw = torch.empty_like(weight, memory_format=torch.contiguous_format)
             gb = torch.empty(cout, dtype=torch.float32, device=dev) if has_bias and ctx.needs_input_grad[2] else None
-            ig.make_wgrad_launch(xp, 0, Cin, gp, 0, cout, k, stride, padding, transposed=transposed, dw=gw, db=gb)()
+            ig.make_wgrad_launch(xp, 0, Cin, gp, 0, cout, k, stride, padding, transposed=transposed, dw=gw, db=gb, dilation=dilation)()
             if not ctx.needs_input_grad[1]:
                 gw = None
-        return gx, gw, gb, None, None, None, None
+        return gx, gw, gb, None, None, None, None, None
 
 
 def _native_train_block(x, conv, slope: float):
     """The block `conv` (+ bias + LeakyReLU(slope)) on `_NativeTrainConv`; geometry outside its scope is an error, not a fallback."""
     transposed = isinstance(conv, torch.nn.ConvTranspose2d)
-    k, s, p = conv.kernel_size, conv.stride, conv.padding
-    ok = (k[0] == k[1] and s[0] == s[1] and p[0] == p[1] and conv.dilation == (1, 1) and conv.groups == 1
+    k, s, p, d = conv.kernel_size, conv.stride, conv.padding, conv.dilation
+    ok = (k[0] == k[1] and s[0] == s[1] and p[0] == p[1] and d[0] == d[1] and d[0] >= 1 and conv.groups == 1
           and conv.weight.dtype == torch.float32)
+    # a dilation: stride-1 convolutions of up to 5 x 5 only (what the igemm data gradient takes) -- PWC-Net's dc_conv2 .. dc_conv5
+    ok = ok and (d[0] == 1 or (not transposed and s[0] == 1 and k[0] * k[1] <= L.UFR_IGEMM_MAX_TAPS
+                               and min(x.shape[2], x.shape[3]) + 2 * p[0] >= (k[0] - 1) * d[0] + 1))
     B, Cin, H, W = x.shape
     if transposed:
         ok = ok and (k[0], s[0], p[0]) == (4, 2, 1) and conv.output_padding == (0, 0)
@@ -328,8 +336,9 @@ def _native_train_block(x, conv, slope: float):
     if not ok:
         raise NotImplementedError(f"band_conv.native_training: {conv} on a {H} x {W} input is outside the native training path "
                                   "(square kernels up to 5 x 5 or the 7 x 7 stride-2 stem on three channels, stride 1 or 2 on even "
-                                  "sides, no dilation or groups, ConvTranspose2d(., ., 4, 2, 1))")
-    return _NativeTrainConv.apply(x.contiguous(), conv.weight, conv.bias, transposed, s[0], p[0], float(slope))
+                                  "sides, a square dilation at stride 1 only (a strided or transposed layer takes none), no groups, "
+                                  "ConvTranspose2d(., ., 4, 2, 1))")
+    return _NativeTrainConv.apply(x.contiguous(), conv.weight, conv.bias, transposed, s[0], p[0], float(slope), d[0])
 
 
 def flow_head(x, conv: torch.nn.Conv2d):
@@ -367,7 +376,8 @@ class FlowHead(torch.nn.Conv2d):
 
 
 class FlowUpsample(torch.nn.ConvTranspose2d):
-    """`upsampled_flow*` / PWC-Net's `deconv*`: a ConvTranspose2d that runs `flow_upsample`."""
+    """`upsampled_flow*` / PWC-Net's `deconv*` and `upfeat*`: a ConvTranspose2d that runs `flow_upsample` (more than two input
+    channels: the native training block inside `native_training()`, `F.conv_transpose2d` with the module's own arguments otherwise)."""
 
     def forward(self, x, output_size=None):
         return flow_upsample(x, self)

@@ -1,5 +1,6 @@
 // igemm_wgrad.hip -- the WEIGHT gradient of the convolutions igemm.hip runs forward and backward-data:
-//   dW[n][c][ky][kx] = sum over (b, y, x) of gy[b, n, y, x] * x[b, c, y*sy + ky - py, x*sx + kx - px]      (zero outside [0,Hi) x [0,Wi))
+//   dW[n][c][ky][kx] = sum over (b, y, x) of gy[b, n, y, x] * x[b, c, y*sy + ky*dy - py, x*sx + kx*dx - px]   (zero outside [0,Hi) x [0,Wi))
+// (dy, dx = the dilation: data, as in igemm.hip -- PWC-Net's context network runs 2, 4, 8 and 16)
 // from two operands already in the plane layout (bf16 [3][chunks][M][32], v = p0 + p1 + p2 exactly), float32-accurate on the bf16
 // matrix cores: the six plane products of igemm.hip, in its order (smallest first), accumulated in float32 by
 // `v_mfma_f32_32x32x16_bf16`.
@@ -11,7 +12,7 @@
 // (4 pixels x 16 channels per 16-lane group, delivered channel-major): lane l of the wave gets channel l & 31, pixels
 // 8 (l >> 5) + 0..7 of a 16-pixel k step from two reads.  A 32-lane half reads 4 whole rows = 256 contiguous bytes: no bank
 // conflict.  Tap rows outside the frame and the pixels behind a slice's end are ZEROS WRITTEN TO LDS; they are never read from
-// memory.  The transposed reads sit in workgroup-uniform control flow (EXEC all ones).
+// memory (with a dilation as large as the grid whole taps lie outside: their workgroups stage zeros only and write exact zeros).  The transposed reads sit in workgroup-uniform control flow (EXEC all ones).
 //
 // Workgroup = 256 threads, one (n tile, c tile, tap, pixel slice): 64 NB output channels x 64 input channels, four waves 2 x 2,
 // a wave owns NB 32 x 32 blocks.  The next K tile's 16-byte pieces are fetched into registers before the current tile's MFMAs.
@@ -40,7 +41,7 @@ __device__ constexpr int PROD_X[6] = {0, 2, 1, 0, 1, 0};
 struct WArgs {
   const __bf16* x; long x_plane_stride; int x_chunk0, C, CCH;      // CCH = chunks that hold the C channels
   const __bf16* g; long g_plane_stride; int g_chunk0, N, NCH;
-  int B, Hi, Wi, Ho, Wo, kw, sy, sx, py, px, taps;
+  int B, Hi, Wi, Ho, Wo, kw, sy, sx, py, px, dy, dx, taps;
   int M, per;                        // pixels of the gy grid; pixels per slice (a multiple of KT)
   int tiles_c;
   float* out; long slab;             // direct: dw (slab = 0); split: the workspace and the floats of one slab
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WArgs a) {
     long xpix = -1;
     if (live) {
       const int b = m / hw, r = m - b * hw, y = r / a.Wo, xx = r - y * a.Wo;
-      const int yi = y * a.sy + ky - a.py, xi = xx * a.sx + kx - a.px;
+      const int yi = y * a.sy + ky * a.dy - a.py, xi = xx * a.sx + kx * a.dx - a.px;
       if ((unsigned)yi < (unsigned)a.Hi && (unsigned)xi < (unsigned)a.Wi) xpix = ((long)b * a.Hi + yi) * a.Wi + xi;
     }
 #pragma unroll
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, long
 
 }  // namespace
 
-extern "C" int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t stream) {
+extern "C" int ufr_igemm_wgrad_dilated(const ufr_igemm_wgrad_desc* d, int dy, int dx, ufr_stream_t stream) {
   UFR_REQUIRE(d, "igemm wgrad: null descriptor");
   UFR_REQUIRE(d->x && d->gy && d->dw, "igemm wgrad: null pointer (x, gy and dw are required)");
   UFR_REQUIRE(d->products == 6, "igemm wgrad: products must be 6 (the float32-accurate form is the only one), got %d", d->products);
@@ -195,11 +196,13 @@ extern "C" int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t strea
               (long)d->kh * d->kw, MAX_TAPS);
   UFR_REQUIRE(d->B > 0 && d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0, "igemm wgrad: bad grid");
   UFR_REQUIRE(d->sy > 0 && d->sx > 0 && d->py >= 0 && d->px >= 0, "igemm wgrad: bad stride / padding");
+  UFR_REQUIRE(dy >= 1 && dx >= 1, "igemm wgrad: bad dilation %d x %d (at least 1)", dy, dx);
   UFR_REQUIRE(d->C > 0 && d->N > 0 && d->in_chunk0 >= 0 && d->g_chunk0 >= 0, "igemm wgrad: bad channel counts");
   const long Min = (long)d->B * d->Hi * d->Wi, M = (long)d->B * d->Ho * d->Wo;
   UFR_REQUIRE(Min < (1L << 30) && M < (1L << 30), "igemm wgrad: too many pixels");
   // the taps must stay inside int arithmetic and the frame's neighbourhood: the last output cell's last tap
-  UFR_REQUIRE((long)(d->Ho - 1) * d->sy + d->kh < (1L << 30) && (long)(d->Wo - 1) * d->sx + d->kw < (1L << 30), "igemm wgrad: bad geometry");
+  UFR_REQUIRE((long)(d->Ho - 1) * d->sy + (long)(d->kh - 1) * dy + 1 < (1L << 30) && (long)(d->Wo - 1) * d->sx + (long)(d->kw - 1) * dx + 1 < (1L << 30),
+              "igemm wgrad: bad geometry (the last tap of the last output cell, dilation %d x %d, leaves int arithmetic)", dy, dx);
   const int CCH = (d->C + 31) / 32, NCH = (d->N + 31) / 32;
   if (d->x_plane_stride <= 0 || (long)(d->in_chunk0 + CCH) * Min * 32 > d->x_plane_stride)
     return ufr::fail(UFR_EINVAL, "igemm wgrad: chunks [%d, %d) leave the x planes operand (%ld chunks per plane)", d->in_chunk0,
@@ -220,7 +223,7 @@ extern "C" int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t strea
   a.x = static_cast<const __bf16*>(d->x); a.x_plane_stride = d->x_plane_stride; a.x_chunk0 = d->in_chunk0; a.C = d->C; a.CCH = CCH;
   a.g = static_cast<const __bf16*>(d->gy); a.g_plane_stride = d->gy_plane_stride; a.g_chunk0 = d->g_chunk0; a.N = d->N; a.NCH = NCH;
   a.B = d->B; a.Hi = d->Hi; a.Wi = d->Wi; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw;
-  a.sy = d->sy; a.sx = d->sx; a.py = d->py; a.px = d->px; a.taps = taps;
+  a.sy = d->sy; a.sx = d->sx; a.py = d->py; a.px = d->px; a.dy = dy; a.dx = dx; a.taps = taps;
   a.M = (int)M;
   a.per = (int)(((M + d->splitm - 1) / d->splitm + KT - 1) / KT * KT);
   a.tiles_c = (CCH + XCH - 1) / XCH;
@@ -249,3 +252,5 @@ extern "C" int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t strea
   wgrad_reduce_kernel<<<ufr::stream_grid(d->N, 256), 256, 0, st>>>(d->ws + dw_elems, slab, d->splitm, d->db, d->N, d->accumulate ? 1 : 0);
   return ufr::launched("igemm_wgrad_reduce_kernel (bias)");
 }
+
+extern "C" int ufr_igemm_wgrad(const ufr_igemm_wgrad_desc* d, ufr_stream_t stream) { return ufr_igemm_wgrad_dilated(d, 1, 1, stream); }

@@ -117,7 +117,7 @@ class PWCDCNet(nn.Module):
             setattr(self, f"predict_flow{lvl}", FlowHead(int(od + dd[4]), 2, 3, 1, 1, bias=True))
             setattr(self, f"deconv{lvl}", FlowUpsample(2, 2, 4, 2, 1, bias=True))
             if lvl > 2:
-                setattr(self, f"upfeat{lvl}", nn.ConvTranspose2d(int(od + dd[4]), 2, 4, 2, 1, bias=True))
+                setattr(self, f"upfeat{lvl}", FlowUpsample(int(od + dd[4]), 2, 4, 2, 1, bias=True))
         od = nd + 32 + 4
         for i, (cin, cout, dil) in enumerate(((od + dd[4], 128, 1), (128, 128, 2), (128, 128, 4), (128, 96, 8),
                                               (96, 64, 16), (64, 32, 1)), start=1):

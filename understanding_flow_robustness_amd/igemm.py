@@ -536,15 +536,18 @@ def splitk_for(M: int, Npad: int, ktiles: int, phases: int = 1, target: int = 76
 
 # ---------------------------------------------------------------------------------------------------- weight gradient
 class WgradLaunch(Launch):
-    """One prepared `ufr_igemm_wgrad` call (csrc/igemm_wgrad.hip); a transposed layer with a bias carries a second descriptor."""
+    """One prepared `ufr_igemm_wgrad_dilated` call (csrc/igemm_wgrad.hip); a transposed layer with a bias carries a second
+    descriptor.  The dilation travels beside the descriptor (the C struct has no field for it)."""
 
-    def __init__(self, descs, keep):
+    def __init__(self, descs, keep, dilation=(1, 1)):
         super().__init__(descs[0], keep)
         self.descs = descs
+        self.dilation = dilation
 
     def __call__(self):
+        dy, dx = self.dilation
         for d in self.descs:
-            L.check(L.lib().ufr_igemm_wgrad(C.byref(d), L.stream()), "igemm wgrad")
+            L.check(L.lib().ufr_igemm_wgrad_dilated(C.byref(d), dy, dx, L.stream()), "igemm wgrad")
 
     def algorithmic_bytes(self) -> float:
         """Both operands across HBM once (three bf16 planes each) plus the float32 result."""
@@ -593,17 +596,24 @@ def _wgrad_desc(x, in_chunk0, Cn, gy, g_chunk0, N, kernel, stride, padding, dw, 
 
 def make_wgrad_launch(x: Planes, in_chunk0: int, C: int, gy: Planes, g_chunk0: int, N: int, kernel, stride, padding, *,
                       transposed: bool = False, dw: torch.Tensor, db: torch.Tensor | None = None, accumulate: bool = False,
-                      splitm: int | None = None) -> Launch:
-    """The weight gradient of Conv2d(C, N, kernel, stride, padding) from the layer's input planes `x` (chunks [in_chunk0, ...)) and
+                      splitm: int | None = None, dilation=1) -> Launch:
+    """The weight gradient of Conv2d(C, N, kernel, stride, padding, dilation) from the layer's input planes `x` (chunks [in_chunk0, ...)) and
     the planes of its output's gradient `gy` (chunks [g_chunk0, ...)): dw [N, C, kh, kw] float32 (written, or added onto with
     `accumulate`), db [N] = the bias gradient.  The launch owns its split workspace; `splitm` = slices of the pixel range (None: a
     rule of thumb that fills the chip).  Results are bit-reproducible for a given `splitm`.
     transposed=True: ConvTranspose2d(C, N, kernel, 2, padding) with `x` its input on the coarse grid and `gy` the gradient on the
     fine grid -- the same kernel with the operands swapped (csrc/igemm_wgrad.hip), dw [C, N, kh, kw] as torch keeps it; the bias
-    gradient [N] is the `db` of a second, one-tap call whose reduced operand is the fine gradient."""
+    gradient [N] is the `db` of a second, one-tap call whose reduced operand is the fine gradient.
+    `dilation` (an int or a pair, at least 1) spaces the taps of a Conv2d; a transposed layer takes none."""
     keep = [x, gy, dw, db]
+    dil = _pair(dilation)
+    if min(dil) < 1:
+        raise RuntimeError(f"igemm wgrad: bad dilation {dil}")
     if not transposed:
-        return WgradLaunch([_wgrad_desc(x, in_chunk0, C, gy, g_chunk0, N, kernel, stride, padding, dw, db, accumulate, splitm, keep)], keep)
+        return WgradLaunch([_wgrad_desc(x, in_chunk0, C, gy, g_chunk0, N, kernel, stride, padding, dw, db, accumulate, splitm, keep)], keep,
+                           dil)
+    if dil != (1, 1):
+        raise RuntimeError(f"igemm wgrad: a transposed layer with dilation {dil} is not served (dilation 1 only)")
     descs = [_wgrad_desc(gy, g_chunk0, N, x, in_chunk0, C, kernel, stride, padding, dw, None, accumulate, splitm, keep)]
     if db is not None:
         scratch = torch.zeros(N, dtype=torch.float32, device=dw.device)          # dw of the one-tap call: <gy[n], gy[first channel]>, dropped

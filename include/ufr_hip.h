@@ -837,6 +837,62 @@ int ufr_flow_up_planes_forward(const float* x, const float* w, const float* bias
 int ufr_flow_up_planes_backward(const float* G, int chunk, const float* w, float* grad_x, int B, int H, int W,
                                 int accumulate /* ABI 6: grad_x += (1) or = (0) */, ufr_stream_t stream);
 
+/* ---- the rest of the fine-tuning step (additive entries, the ABI version stays) ----------------------------------------------
+ * The two training losses of the reference's `flowNetC or pwc` branch (training/utils.py:68-222), value AND gradient of every
+ * prediction in three launches whatever the frame size (csrc/train_loss.hip):
+ *   gt_i = area_interpolate(gt / div_flow when div_flow > 1, (h_i, w_i)); channel 0 times w_i/W, channel 1 times h_i/H;
+ *   kind 0 (sequence_loss):  loss = sum_i weight[i] * mean over the elements whose gt_i is not NaN of |pred_i - gt_i|;
+ *          grad_i = weight[i] / count_i * sign(pred_i - gt_i), exact 0 where gt_i is NaN;
+ *   kind 1 (multiscale_epe): loss = sum_i weight[i] * mean over the pixels whose gt_i is not NaN in either channel of
+ *          sqrt(sum_c (pred_i - gt_i)^2 + 1e-5); a scale without such a pixel is skipped (its gradient is written as zeros);
+ *          grad_i = weight[i] / count_i * (pred_i - gt_i) / that root, NaN in both channels of a pixel whose gt_i has a NaN.
+ * H and W are integer multiples of every h_i, w_i: the interpolation is the mean of an (H/h_i) x (W/w_i) block, summed in float64
+ * in a fixed order.  gt: float32 [B,2,H,W]; pred[i] / grad[i]: float32 [B,2,h_i,w_i]; ws: ufr_train_loss_workspace_doubles()
+ * doubles (the interpolated ground truths, per-workgroup sums and non-NaN counts: no float atomics, two runs are bit-identical).
+ * out (device, 8 doubles): loss, sum of the scale-0 end-point errors, how many were summed, how many are < 1, < 3, < 5, 0, 0.
+ * The end-point error of the metrics: kind 0 against the scaled gt_0 without any NaN filter (one NaN makes the sum NaN), kind 1
+ * against the UNSCALED interpolated ground truth with NaN entries left out.
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: null pointers, nscale outside 1 .. 8, non-positive sizes, a side of
+ * gt that is not an integer multiple of a prediction's, a kind other than 0 / 1, a workspace that is too small. */
+#define UFR_TRAIN_LOSS_MAX_SCALES 8
+typedef struct {
+  const float* gt; int B, H, W;
+  int nscale;
+  const float* pred[UFR_TRAIN_LOSS_MAX_SCALES];
+  float* grad[UFR_TRAIN_LOSS_MAX_SCALES];
+  int h[UFR_TRAIN_LOSS_MAX_SCALES], w[UFR_TRAIN_LOSS_MAX_SCALES];
+  double weight[UFR_TRAIN_LOSS_MAX_SCALES];
+  int kind;
+  double div_flow;
+  double* ws; long ws_elems;
+  double* out;
+} ufr_train_loss_desc;
+/* -1 when a size is not positive or nscale is outside 1 .. 8 */
+long ufr_train_loss_workspace_doubles(int B, int nscale, const int* h, const int* w);
+int ufr_train_loss(const ufr_train_loss_desc* d, ufr_stream_t stream);
+
+/* torch.nn.utils.clip_grad_norm_ (error_if_nonfinite=False) + torch.optim.AdamW (amsgrad=False, maximize=False) over many
+ * tensors (csrc/optim.hip).  `segs` is a HOST array that is read before the call returns: the segments travel to the kernels BY
+ * VALUE in the kernel arguments, a bounded number per launch -- no device-side table, no copy, no allocation; the number of launches
+ * grows with the number of tensors only.  Segments with n == 0 are skipped; nseg == 0 succeeds and launches nothing.
+ *   ufr_grad_norm: one float64 sum of squares per workgroup into `partials` (ufr_grad_norm_partials() values), then one workgroup
+ *     adds them in a fixed order and writes norm_out[0] = total L2 norm, norm_out[1] = min(1, max_norm / (norm + 1e-6)) (a
+ *     non-finite norm gets no special case).  Bit-reproducible.  Only `g` and `n` of a segment are read.
+ *   ufr_adamw_step: with g' = coef * g (coef = norm[1] read on the device, 1 when norm is NULL; g itself is not rewritten)
+ *     p *= 1 - lr*weight_decay;  m = beta1*m + (1-beta1)*g';  v = beta2*v + (1-beta2)*g'^2;
+ *     p -= (lr / bias1) * m / (sqrt(v)/sqrt(bias2) + eps)          (bias1 = 1 - beta1^t, bias2 = 1 - beta2^t)
+ *     16-byte loads and stores where the four pointers of a segment share their offset modulo 16 bytes (scalar head and tail),
+ *     scalar accesses otherwise.
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: a null `segs` with nseg > 0, nseg < 0, n < 0, a null segment pointer
+ * with n > 0, lr < 0, betas outside [0,1), eps < 0, weight_decay < 0, bias1 / bias2 outside (0,1], a null norm_out, a `partials`
+ * buffer that is null or too small. */
+typedef struct { float* p; const float* g; float* m; float* v; long n; } ufr_adamw_seg;
+typedef struct { double lr, beta1, beta2, eps, weight_decay, bias1, bias2; } ufr_adamw_hyper;
+long ufr_grad_norm_partials(const ufr_adamw_seg* segs, int nseg);   /* -1 for a null `segs` with nseg > 0, nseg < 0 or an n < 0 */
+int ufr_grad_norm(const ufr_adamw_seg* segs, int nseg, float max_norm, double* partials, long partial_elems, float* norm_out,
+                  ufr_stream_t stream);
+int ufr_adamw_step(const ufr_adamw_seg* segs, int nseg, const ufr_adamw_hyper* h, const float* norm, ufr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ Layout (only what the hot path needs):
   flownets/                    the flow networks + registry (fetch_model / predict_flow)
   patch_attack, universal_perturbation, losses
                                the attack inner loops as fused HIP-graph steps
+  training                     the fine-tuning step after the convolutions: sequence_loss / multiscale_epe, ClippedAdamW,
+                               fetch_optimizer, finetune_step (csrc/train_loss.hip, csrc/optim.hip)
 
 `install()` registers the extension mirrors under the reference's top-level module names so the
 reference's own `models/*.py` import them unchanged.

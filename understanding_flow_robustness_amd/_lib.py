@@ -96,6 +96,29 @@ class IgemmWgradDesc(C.Structure):
                 ("products", C.c_int)]
 
 
+UFR_TRAIN_LOSS_MAX_SCALES = 8
+
+
+class TrainLossDesc(C.Structure):
+    """ufr_train_loss_desc (include/ufr_hip.h), field for field."""
+    _fields_ = [("gt", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("nscale", C.c_int),
+                ("pred", C.c_void_p * UFR_TRAIN_LOSS_MAX_SCALES), ("grad", C.c_void_p * UFR_TRAIN_LOSS_MAX_SCALES),
+                ("h", C.c_int * UFR_TRAIN_LOSS_MAX_SCALES), ("w", C.c_int * UFR_TRAIN_LOSS_MAX_SCALES),
+                ("weight", C.c_double * UFR_TRAIN_LOSS_MAX_SCALES),
+                ("kind", C.c_int), ("div_flow", C.c_double),
+                ("ws", C.c_void_p), ("ws_elems", C.c_long), ("out", C.c_void_p)]
+
+
+class AdamwSeg(C.Structure):
+    """ufr_adamw_seg (include/ufr_hip.h)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long)]
+
+
+class AdamwHyper(C.Structure):
+    """ufr_adamw_hyper (include/ufr_hip.h)."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias1", "bias2")]
+
+
 UFR_MAX_CONE_LAYERS = 8
 
 
@@ -233,6 +256,9 @@ SIGNATURES = {
     "ufr_altcorr_planes_prepare": [_vp, _vp, _l, _l, _i, _vp],
     "ufr_altcorr_planes_forward": [_vp, _l, C.POINTER(AltCorrPlaneLevels), _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "ufr_conv1_direct": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _l, _i, _vp],
+    "ufr_train_loss": [C.POINTER(TrainLossDesc), _vp],
+    "ufr_grad_norm": [C.POINTER(AdamwSeg), _i, _f, _vp, _l, _vp, _vp],
+    "ufr_adamw_step": [C.POINTER(AdamwSeg), _i, C.POINTER(AdamwHyper), _vp, _vp],
 }
 PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_device_count": (C.c_int, []), "ufr_build_manifest": (C.c_char_p, []),
@@ -241,7 +267,9 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_cm_norm_workspace_doubles": (C.c_long, [_l, _i, _i]),
          "ufr_resample2d_backward_workspace_bytes": (C.c_long, [_i, _i, _i]),
          "ufr_pwc_warp_backward_workspace_bytes": (C.c_long, [_i, _i, _i]),
-         "ufr_altcorr_pyramid_workspace_bytes": (C.c_long, [_i, _i, _i, _i, _i, _i])}
+         "ufr_altcorr_pyramid_workspace_bytes": (C.c_long, [_i, _i, _i, _i, _i, _i]),
+         "ufr_train_loss_workspace_doubles": (C.c_long, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+         "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i])}
 
 
 def lib():

@@ -219,7 +219,8 @@ class native_training:
     """`with band_conv.native_training():` -- opt-in: inside, `conv_leaky`, `flow_head` and `flow_upsample` run a block whose
     parameters require gradients on the hand-written kernels (HIP float32 tensors, autograd on): forward and data gradient on the
     igemm (csrc/igemm.hip), weight and bias gradient on csrc/igemm_wgrad.hip, instead of `F.conv2d` / `F.conv_transpose2d` on
-    the vendor library.  The fine-tuning half of adversarial training (training/train.py:171-222 of the reference).
+    the vendor library.  These are the convolutions of the fine-tuning iteration of adversarial training (training/train.py:225-282
+    of the reference); its loss, gradient clipping, AdamW and the iteration itself are `training.py` (`finetune_step`).
     Scope: the FlowNetC family and PWC-Net.  `FlowNetC` is fully served (every block of its stem and head); the Robust FlowNetC
     family and FlowNetS come along as far as their blocks go through these three helpers (square kernels up to 5 x 5, or the
     7 x 7 stride-2 stem on three channels; stride 1 or 2; a square dilation on stride-1 layers only; no groups;

@@ -824,6 +824,28 @@ int ufr_flow_head_planes_backward(const float* grad_y, const float* wpk, int w_c
 int ufr_flow_head_planes_backward_finalize(const float* grad_y, const float* wpk, int w_chunks, float* G, int g_chunks, int chunk0,
                                            int chunks, int B, int H, int W, int accumulate, const void* mask_planes, void* out_planes,
                                            long out_plane_stride, int fin_chunk0, int fin_chunks, float slope, ufr_stream_t stream);
+/* The same adjoint for a range of two chunk groups of which only a REGION of the first is ever read (the patch attack's banded
+ * backward: conv2's / conv3_1's / conv4_1's output gradient behind a windowed prefix).  The head group, chunks [chunk0, chunk0 +
+ * head_chunks), is computed on the region's pixels only -- outside it G is neither read nor written, with or without `accumulate`;
+ * the trailing group [chunk0 + head_chunks, chunk0 + chunks) runs over the whole frame, with the fused finalisation of
+ * ufr_flow_head_planes_backward_finalize when `out_planes` is given (fin_chunk0 >= head_chunks).  Inside the region every value
+ * is computed exactly as the unrestricted entry computes it.  One table row of `origin_stride` ints per pair:
+ *   UFR_PF_REGION_BAND    columns [origin[b * origin_stride] / origin_div, + reg_w) of every row (reg_h = H, margin = 0): the
+ *                         triple of ufr_igemm_desc's row_x0 / row_x0_stride / row_x0_div;
+ *   UFR_PF_REGION_WINDOW  the reg_h x reg_w cells at (origin[b * origin_stride] / origin_div, origin[b * origin_stride + 1] /
+ *                         origin_div), without the inexact rim of `margin` cells (ufr_window_gather's rule: an edge that is the
+ *                         frame's edge has no rim).
+ * Either origin is clamped into the frame as ufr_window_gather clamps it.  `head_out` (window regions only, NULL otherwise): the
+ * head group leaves as the chunk-major window tensor [head_chunks][head_out_images * reg_h * reg_w][32] instead, rim zeroed --
+ * what ufr_window_gather_chunks makes of the unrestricted result -- always written, never added to; G's head chunks are then
+ * not touched at all. */
+#define UFR_PF_REGION_BAND 1
+#define UFR_PF_REGION_WINDOW 2
+int ufr_flow_head_planes_backward_regions(const float* grad_y, const float* wpk, int w_chunks, float* G, int g_chunks, int chunk0,
+                                          int chunks, int B, int H, int W, int accumulate, int head_chunks, int region,
+                                          const int* origin, int origin_stride, int origin_div, int reg_h, int reg_w, int margin,
+                                          float* head_out, int head_out_images, const void* mask_planes, void* out_planes,
+                                          long out_plane_stride, int fin_chunk0, int fin_chunks, float slope, ufr_stream_t stream);
 /* PWC-Net's `upfeat*` = ConvTranspose2d(C, 2, 4, 2, 1) (models/PWCNet.py:115-143, used at :284,:299,:314,:329) on the engine's planes:
  * forward from `chunks` chunks of the COARSE [B,H,W] planes to out [B,2,2H,2W] (NCHW fp32, + bias) on the matrix cores
  * (wmf: bf16 [chunks][3][2][16][32] with n = 2 (4 ky + kx) + o); backward from grad_y [B,2,2H,2W] into the coarse gradient

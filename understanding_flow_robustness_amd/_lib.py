@@ -120,6 +120,7 @@ class AdamwHyper(C.Structure):
 
 
 UFR_MAX_CONE_LAYERS = 8
+UFR_PF_REGION_BAND, UFR_PF_REGION_WINDOW = 1, 2      # region kinds of ufr_flow_head_planes_backward_regions
 
 
 class ConeChain(C.Structure):
@@ -213,6 +214,8 @@ SIGNATURES = {
     "ufr_deconv_flow_tail_backward_mfma": [_vp, _l, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "ufr_flow_head_planes_backward": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ufr_flow_head_planes_backward_finalize": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _l, _i, _i, _f, _vp],
+    "ufr_flow_head_planes_backward_regions": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _i,
+                                              _vp, _vp, _l, _i, _i, _f, _vp],
     "ufr_unshuffle_pack_planes": [_vp, _vp, _l, _i, _i, _i, _i, _vp],
     "ufr_unshuffle_unpack_grad": [_vp, _vp, _i, _i, _i, _i, _vp],
     "ufr_conv3x3s2_c3_planes": [_vp, _vp, _vp, _f, _vp, _l, _i, _i, _i, _i, _i, _vp],

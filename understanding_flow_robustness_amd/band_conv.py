@@ -18,12 +18,30 @@ import torch.nn.functional as F
 from . import _lib as L
 
 
+CORR_REACH = 160      # pixels: the 21 x 21 correlation with dilation 2 at 1/8 resolution reaches 20 cells to either side
+
+
+def corr_band_width(ww: int, reach: int = CORR_REACH) -> int:
+    """Width in pixels (a multiple of 32) of the narrowest column band that holds a `ww`-pixel window and `reach` pixels to
+    either side of it for every placement, an origin clamped at a frame edge included."""
+    return -(-(int(ww) + 2 * reach) // 32) * 32
+
+
+def corr_band_origin(x0, width: int, W: int, reach: int = CORR_REACH):
+    """First pixel column of that band for a window that starts at `x0` (a multiple of 8: an int, or an int32 tensor of
+    one origin per pair): `reach` to the left of the window, inside the frame.  A multiple of 8 when x0, reach, W and width are;
+    [origin, origin + width) holds [x0 - reach, x0 + ww + reach) cut to the frame for every ww <= width - 2 reach."""
+    lo = x0 - reach
+    return lo.clamp(0, W - width) if torch.is_tensor(lo) else min(max(lo, 0), W - width)
+
+
 class Band:
     """A per-sample column band: `win` int32 [B,8] with win[:,1] = first pixel column (win[:,0] = 0), `width`
-    pixels wide; both multiples of every level stride the band is used at."""
+    pixels wide; both multiples of every level stride the band is used at.  `corr_width` (0 = none): a second, narrower band
+    inside it, from win[:,2], for the two data gradients that only the window's correlation adjoint reads (multiples of 8)."""
 
     def __init__(self, win: torch.Tensor, width: int, cone_win: torch.Tensor | None = None, cone_hw=None):
-        self.win, self.width = win, int(width)
+        self.win, self.width, self.corr_width = win, int(width), 0
         # the prefix window itself (pixels): the correlation's adjoint is needed on its cells only
         self.cone_win, self.cone_hw = cone_win, cone_hw
         # incremental forward (second and later iterations of an attack() call): the blocks named in

@@ -7,6 +7,9 @@
 //                          weights repacked [chunk][tap][out][32]; the four groups of a pixel are added by two shuffles
 //   flow_head_planes_bwd   thread = (pixel, 8-channel group): the pixel's 3x3x2 gradient neighbourhood in registers,
 //                          per chunk 144 FMAs and one 32-byte store (or read-add-store) into the fp32 gradient sum
+//   flow_head_planes_bwd_regions   the same per pixel over two chunk groups in one launch: the leading group on a column band or
+//                          a window rectangle per pair only (the patch attack's banded backward reads nothing else of it; a window
+//                          can leave as a window-sized tensor, rim zeroed), the trailing group over the frame
 //   flow_up_planes_fwd     ConvTranspose2d(2,2,4,2,1) written straight into the concatenation's last chunk (2 channels
 //                          + 30 zeros, all three planes)
 //   flow_up_planes_bwd     its data gradient from channels 0-1 of that chunk of the fp32 gradient sum
@@ -349,6 +352,72 @@ struct PfFinalize {
   const __bf16* mask; __bf16* out; long out_plane_stride; int c0, n; float slope;
 };
 
+// the pixel's 3x3x2 gradient neighbourhood: tap k of the output pixel that used it on this input pixel
+__device__ __forceinline__ void pf_bwd_taps(const float* __restrict__ gy, long b, int yy, int xx, int H, int W, float (&g0)[9],
+                                            float (&g1)[9]) {
+  const long HW = (long)H * W;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int y2 = yy - (k / 3 - 1), x2 = xx - (k % 3 - 1);
+    const bool ok = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
+    g0[k] = ok ? gy[(b * 2 + 0) * HW + (long)y2 * W + x2] : 0.f;
+    g1[k] = ok ? gy[(b * 2 + 1) * HW + (long)y2 * W + x2] : 0.f;
+  }
+}
+
+// one chunk's eight channels of this thread (wc = the chunk's [9][2][32] weights in LDS + the thread's channel offset)
+__device__ __forceinline__ void pf_bwd_chunk(const float* wc, const float (&g0)[9], const float (&g1)[9], float4& lo, float4& hi) {
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float4 w0a = *reinterpret_cast<const float4*>(wc + (k * 2 + 0) * 32), w0b = *reinterpret_cast<const float4*>(wc + (k * 2 + 0) * 32 + 4);
+    const float w0[8] = {w0a.x, w0a.y, w0a.z, w0a.w, w0b.x, w0b.y, w0b.z, w0b.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = fmaf(g0[k], w0[j], a[j]);
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float4 w1a = *reinterpret_cast<const float4*>(wc + (k * 2 + 1) * 32), w1b = *reinterpret_cast<const float4*>(wc + (k * 2 + 1) * 32 + 4);
+    const float w1[8] = {w1a.x, w1a.y, w1a.z, w1a.w, w1b.x, w1b.y, w1b.z, w1b.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = fmaf(g1[k], w1[j], a[j]);
+  }
+  lo = make_float4(a[0], a[1], a[2], a[3]);
+  hi = make_float4(a[4], a[5], a[6], a[7]);
+}
+
+// (lo, hi) -> dst[0..8), added onto what is there when `accumulate`; (lo, hi) leave as the stored sum
+__device__ __forceinline__ void pf_bwd_store(float* p, int accumulate, float4& lo, float4& hi) {
+  float4* dst = reinterpret_cast<float4*>(p);
+  if (accumulate) {
+    const float4 o0 = dst[0], o1 = dst[1];
+    lo.x += o0.x; lo.y += o0.y; lo.z += o0.z; lo.w += o0.w;
+    hi.x += o1.x; hi.y += o1.y; hi.z += o1.z; hi.w += o1.w;
+  }
+  dst[0] = lo;
+  dst[1] = hi;
+}
+
+// the completed sum x LeakyReLU'(mask) as the three gradient planes, element e of the tensor
+__device__ __forceinline__ void pf_bwd_finalize(const PfFinalize& fin, long e, const float4& lo, const float4& hi) {
+  float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  if (fin.mask) {
+    const bf16x8 m = *reinterpret_cast<const bf16x8*>(fin.mask + e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = ((float)m[j] > 0.f) ? v[j] : v[j] * fin.slope;
+  }
+  bf16x8 q0, q1, q2;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    __bf16 x, y, z;
+    split3(v[j], x, y, z);
+    q0[j] = x; q1[j] = y; q2[j] = z;
+  }
+  *reinterpret_cast<bf16x8*>(fin.out + e) = q0;
+  *reinterpret_cast<bf16x8*>(fin.out + e + fin.out_plane_stride) = q1;
+  *reinterpret_cast<bf16x8*>(fin.out + e + 2 * fin.out_plane_stride) = q2;
+}
+
 __global__ __launch_bounds__(256) void flow_head_planes_bwd(const float* __restrict__ gy, const float* __restrict__ wpk,
                                                             float* __restrict__ G, int chunk0, int chunks, int B, int H, int W,
                                                             int accumulate, int per, const PfFinalize fin) {
@@ -365,58 +434,99 @@ __global__ __launch_bounds__(256) void flow_head_planes_bwd(const float* __restr
   const long HW = (long)H * W, b = pix / HW, p = pix - b * HW;
   const int yy = (int)(p / W), xx = (int)(p - (long)yy * W);
   float g0[9], g1[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {                       // the output pixel that used tap k on this input pixel
-    const int y2 = yy - (k / 3 - 1), x2 = xx - (k % 3 - 1);
-    const bool ok = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
-    g0[k] = ok ? gy[(b * 2 + 0) * HW + (long)y2 * W + x2] : 0.f;
-    g1[k] = ok ? gy[(b * 2 + 1) * HW + (long)y2 * W + x2] : 0.f;
-  }
+  pf_bwd_taps(gy, b, yy, xx, H, W, g0, g1);
   for (int ch = c_lo; ch < c_hi; ++ch) {
-    const float* wc = lds_w + (ch - c_lo) * 576 + q * 8;
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float4 w0a = *reinterpret_cast<const float4*>(wc + (k * 2 + 0) * 32), w0b = *reinterpret_cast<const float4*>(wc + (k * 2 + 0) * 32 + 4);
-      const float w0[8] = {w0a.x, w0a.y, w0a.z, w0a.w, w0b.x, w0b.y, w0b.z, w0b.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] = fmaf(g0[k], w0[j], a[j]);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float4 w1a = *reinterpret_cast<const float4*>(wc + (k * 2 + 1) * 32), w1b = *reinterpret_cast<const float4*>(wc + (k * 2 + 1) * 32 + 4);
-      const float w1[8] = {w1a.x, w1a.y, w1a.z, w1a.w, w1b.x, w1b.y, w1b.z, w1b.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) a[j] = fmaf(g1[k], w1[j], a[j]);
-    }
-    float4* dst = reinterpret_cast<float4*>(G + ((long)(chunk0 + ch) * M + pix) * 32 + q * 8);
-    float4 lo = make_float4(a[0], a[1], a[2], a[3]), hi = make_float4(a[4], a[5], a[6], a[7]);
-    if (accumulate) {
-      const float4 o0 = dst[0], o1 = dst[1];
-      lo.x += o0.x; lo.y += o0.y; lo.z += o0.z; lo.w += o0.w;
-      hi.x += o1.x; hi.y += o1.y; hi.z += o1.z; hi.w += o1.w;
-    }
-    dst[0] = lo;
-    dst[1] = hi;
-    if (fin.out && ch >= fin.c0 && ch < fin.c0 + fin.n) {
-      const long e = ((long)(chunk0 + ch) * M + pix) * 32 + q * 8;
-      float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-      if (fin.mask) {
-        const bf16x8 m = *reinterpret_cast<const bf16x8*>(fin.mask + e);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = ((float)m[j] > 0.f) ? v[j] : v[j] * fin.slope;
+    float4 lo, hi;
+    pf_bwd_chunk(lds_w + (ch - c_lo) * 576 + q * 8, g0, g1, lo, hi);
+    const long e = ((long)(chunk0 + ch) * M + pix) * 32 + q * 8;
+    pf_bwd_store(G + e, accumulate, lo, hi);
+    if (fin.out && ch >= fin.c0 && ch < fin.c0 + fin.n) pf_bwd_finalize(fin, e, lo, hi);
+  }
+}
+
+// The same adjoint over two chunk groups (ufr_flow_head_planes_backward_regions): the HEAD group [0, head_chunks) of the range on the
+// pixels of a region only -- a column band or a window rectangle per pair, origins in device memory -- the TRAILING group over the
+// frame, finalisation included.  One launch; the grid is the two groups' (pixel blocks x chunk slices) laid end to end over
+// blockIdx.x, so that the head group brings the region's blocks only.  Per pixel the arithmetic is flow_head_planes_bwd's.
+struct PfRegion {
+  int kind;                                  // UFR_PF_REGION_BAND / UFR_PF_REGION_WINDOW
+  const int* origin; int stride, div;        // one row of `stride` ints per pair: band [x0]; window [y0, x0]; cells = value / div
+  int rh, rw, margin;                        // the region in cells (band: rh = H)
+  float* out; int out_images;                // window: the head group as a window tensor [head_chunks][out_images * rh * rw][32]
+  int head_chunks, head_per, head_bx, head_slices, tail_per, tail_bx;
+};
+
+__global__ __launch_bounds__(256) void flow_head_planes_bwd_regions(const float* __restrict__ gy, const float* __restrict__ wpk,
+                                                                    float* __restrict__ G, int chunk0, int chunks, int B, int H, int W,
+                                                                    int accumulate, const PfRegion reg, const PfFinalize fin) {
+  extern __shared__ __attribute__((aligned(16))) float lds_w[];          // this slice's [per][9][2][32]
+  const long M = (long)B * H * W;
+  const int head_blocks = reg.head_bx * reg.head_slices;
+  const bool head = (int)blockIdx.x < head_blocks;
+  int c_lo, c_hi, xblk;
+  if (head) {
+    const int slice = blockIdx.x / reg.head_bx;
+    xblk = blockIdx.x - slice * reg.head_bx;
+    c_lo = slice * reg.head_per;
+    c_hi = min(reg.head_chunks, c_lo + reg.head_per);
+  } else {
+    const int r = blockIdx.x - head_blocks, slice = r / reg.tail_bx;
+    xblk = r - slice * reg.tail_bx;
+    c_lo = reg.head_chunks + slice * reg.tail_per;
+    c_hi = min(chunks, c_lo + reg.tail_per);
+  }
+  for (int i = threadIdx.x; i < (c_hi - c_lo) * 576 / 4; i += blockDim.x)
+    reinterpret_cast<float4*>(lds_w)[i] = reinterpret_cast<const float4*>(wpk + (long)c_lo * 576)[i];
+  __syncthreads();
+  const long t = (long)xblk * blockDim.x + threadIdx.x;
+  const long r = t >> 2;
+  const int q = (int)(t & 3);
+  long b;
+  int yy, xx;
+  if (!head) {
+    if (r >= M) return;
+    const long HW = (long)H * W, p = r % HW;
+    b = r / HW;
+    yy = (int)(p / W); xx = (int)(p - (long)yy * W);
+  } else if (reg.kind == UFR_PF_REGION_BAND) {
+    const long per = (long)H * reg.rw;
+    if (r >= (long)B * per) return;
+    b = r / per;
+    const int p = (int)(r - b * per);
+    yy = p / reg.rw;
+    xx = min(max(reg.origin[b * reg.stride] / reg.div, 0), W - reg.rw) + (p - yy * reg.rw);
+  } else {
+    const long per = (long)reg.rh * reg.rw;
+    if (r >= (long)B * per) return;
+    b = r / per;
+    const int p = (int)(r - b * per), ii = p / reg.rw, j = p - ii * reg.rw;
+    const int* w = reg.origin + b * reg.stride;
+    const int y0 = min(max(w[0] / reg.div, 0), H - reg.rh), x0 = min(max(w[1] / reg.div, 0), W - reg.rw);
+    const bool rim = (ii < reg.margin && y0 > 0) || (ii >= reg.rh - reg.margin && y0 + reg.rh < H) ||
+                     (j < reg.margin && x0 > 0) || (j >= reg.rw - reg.margin && x0 + reg.rw < W);
+    yy = y0 + ii; xx = x0 + j;
+    if (reg.out) {                           // the window tensor: always written, the rim as zeros
+      float g0[9], g1[9];
+      if (!rim) pf_bwd_taps(gy, b, yy, xx, H, W, g0, g1);
+      const long Mw = (long)reg.out_images * per;
+      for (int ch = c_lo; ch < c_hi; ++ch) {
+        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+        if (!rim) pf_bwd_chunk(lds_w + (ch - c_lo) * 576 + q * 8, g0, g1, lo, hi);
+        pf_bwd_store(reg.out + ((long)ch * Mw + b * per + p) * 32 + q * 8, 0, lo, hi);
       }
-      bf16x8 q0, q1, q2;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        __bf16 x, y, z;
-        split3(v[j], x, y, z);
-        q0[j] = x; q1[j] = y; q2[j] = z;
-      }
-      *reinterpret_cast<bf16x8*>(fin.out + e) = q0;
-      *reinterpret_cast<bf16x8*>(fin.out + e + fin.out_plane_stride) = q1;
-      *reinterpret_cast<bf16x8*>(fin.out + e + 2 * fin.out_plane_stride) = q2;
+      return;
     }
+    if (rim) return;
+  }
+  const long pix = (b * H + yy) * W + xx;
+  float g0[9], g1[9];
+  pf_bwd_taps(gy, b, yy, xx, H, W, g0, g1);
+  for (int ch = c_lo; ch < c_hi; ++ch) {
+    float4 lo, hi;
+    pf_bwd_chunk(lds_w + (ch - c_lo) * 576 + q * 8, g0, g1, lo, hi);
+    const long e = ((long)(chunk0 + ch) * M + pix) * 32 + q * 8;
+    pf_bwd_store(G + e, accumulate, lo, hi);
+    if (!head && fin.out && ch >= fin.c0 && ch < fin.c0 + fin.n) pf_bwd_finalize(fin, e, lo, hi);
   }
 }
 
@@ -719,6 +829,55 @@ extern "C" int ufr_flow_head_planes_backward_finalize(const float* grad_y, const
                        PfFinalize{static_cast<const __bf16*>(mask_planes), static_cast<__bf16*>(out_planes), out_plane_stride, fin_chunk0,
                                   fin_chunks, slope},
                        ufr::as_stream(stream));
+}
+
+extern "C" int ufr_flow_head_planes_backward_regions(const float* grad_y, const float* wpk, int w_chunks, float* G, int g_chunks, int chunk0,
+                                                     int chunks, int B, int H, int W, int accumulate, int head_chunks, int region,
+                                                     const int* origin, int origin_stride, int origin_div, int reg_h, int reg_w,
+                                                     int margin, float* head_out, int head_out_images, const void* mask_planes,
+                                                     void* out_planes, long out_plane_stride, int fin_chunk0, int fin_chunks, float slope,
+                                                     ufr_stream_t stream) {
+  const char* what = "flow head (planes) backward, regions";
+  UFR_REQUIRE(grad_y && wpk && G && origin, "%s: null pointer", what);
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && chunks > 0 && chunks <= 48 && chunk0 >= 0 && (long)B * H * W < (1L << 29), "%s: bad shape", what);
+  UFR_REQUIRE_GRANGE("flow head (planes) backward, regions", chunk0, chunks, w_chunks, g_chunks);
+  UFR_REQUIRE(head_chunks > 0 && head_chunks <= chunks, "%s: the head group is %d of %d chunks", what, head_chunks, chunks);
+  UFR_REQUIRE(region == UFR_PF_REGION_BAND || region == UFR_PF_REGION_WINDOW, "%s: region kind %d", what, region);
+  UFR_REQUIRE(origin_div > 0 && reg_w > 0 && reg_w <= W && reg_h > 0 && reg_h <= H, "%s: region %d x %d does not fit %d x %d", what,
+              reg_h, reg_w, H, W);
+  if (region == UFR_PF_REGION_BAND) {
+    UFR_REQUIRE(origin_stride >= 1 && reg_h == H && margin == 0 && !head_out, "%s: a band spans every row, has no rim and stays in G", what);
+  } else {
+    UFR_REQUIRE(origin_stride >= 2 && margin >= 0 && 2 * margin <= reg_h && 2 * margin <= reg_w, "%s: bad window stride / margin", what);
+    UFR_REQUIRE(!head_out || head_out_images >= B, "%s: the window tensor holds %d images, the range %d", what, head_out_images, B);
+  }
+  PfFinalize fin{nullptr, nullptr, 0, 0, 0, 1.f};
+  if (out_planes) {
+    UFR_REQUIRE(planes_hold(out_plane_stride, (long)B * H * W, chunk0 + fin_chunk0, fin_chunks),
+                "%s: the finalised segment leaves the gradient planes", what);
+    UFR_REQUIRE(fin_chunk0 >= head_chunks && fin_chunks > 0 && fin_chunk0 + fin_chunks <= chunks && out_plane_stride > 0,
+                "%s: the finalised segment leaves the trailing group", what);
+    fin = PfFinalize{static_cast<const __bf16*>(mask_planes), static_cast<__bf16*>(out_planes), out_plane_stride, fin_chunk0, fin_chunks, slope};
+  }
+  // each group sliced over its chunks by launch_pf_bwd's rule, on its own pixel count
+  auto slice = [](long pixels, int n, int& bx, int& per, int& slices) {
+    bx = ufr::ceil_div(pixels * 4, 256);
+    slices = 1;
+    while ((long)bx * slices < 1024 && slices < n) slices *= 2;
+    if (slices > n) slices = n;
+    per = ufr::ceil_div(n, slices);
+    slices = ufr::ceil_div(n, per);
+  };
+  PfRegion reg{region, origin, origin_stride, origin_div, reg_h, reg_w, margin, head_out, head_out_images, head_chunks, 0, 0, 0, 1, 1};
+  const int tail_chunks = chunks - head_chunks;
+  int tail_slices = 0;
+  slice((long)B * reg_h * reg_w, head_chunks, reg.head_bx, reg.head_per, reg.head_slices);
+  if (tail_chunks > 0) slice((long)B * H * W, tail_chunks, reg.tail_bx, reg.tail_per, tail_slices);
+  const int per = reg.head_per > reg.tail_per || tail_chunks == 0 ? reg.head_per : reg.tail_per;
+  (void)ufr::ensure_dynamic_lds(reinterpret_cast<const void*>(flow_head_planes_bwd_regions), 48 * 576 * 4);
+  flow_head_planes_bwd_regions<<<dim3(reg.head_bx * reg.head_slices + reg.tail_bx * tail_slices), 256, (size_t)per * 576 * 4,
+                                 ufr::as_stream(stream)>>>(grad_y, wpk, G, chunk0, chunks, B, H, W, accumulate, reg, fin);
+  return ufr::launched("flow_head_planes_bwd_regions");
 }
 
 extern "C" int ufr_flow_up_planes_forward(const float* x, const float* w, const float* bias, void* planes, long plane_stride,

@@ -199,6 +199,7 @@ class FlowNetCHeadEngine:
         self._plans = {("fwd", k): plans[i] for k, i in fwd.items()}
         self._plans.update({("bwd", k): plans[i] for k, i in bwd.items()})
         self._band, self.fwd_band, self.bwd_band = None, {}, {}
+        self.bwd_band_wide, self.bwd_rest, self._band_plans, self._pf_band, self._split_w = {}, {}, {}, {}, {}
         # 2-channel layers
         self.pf_w = {k: _pack_flow_head(getattr(net, f"predict_flow{k}").weight) for k, _ in _HEADS}
         self.pf_wm = {k: _pack_flow_head_mfma(getattr(net, f"predict_flow{k}").weight) for k, _ in _HEADS}
@@ -484,6 +485,7 @@ class FlowNetCHeadEngine:
         if self._band is band:
             return
         self._band, self.fwd_band, self.bwd_band = band, {}, {}
+        self.bwd_band_wide, self.bwd_rest, self._band_plans, self._pf_band = {}, {}, {}, {}
         if not band.width:
             return
         W = self.W
@@ -511,10 +513,64 @@ class FlowNetCHeadEngine:
         for name, (ls_rows, ls_in) in self._BWD_BAND.items():
             if ("bwd", name) in self._plans:
                 self.bwd_band[name] = derive("bwd", name, ls_rows, ls_in)
+        if self.siamese:
+            self._attach_unread(band, origin)
+
+    # deconvK's data gradients whose leading columns (conv3_1's / conv4_1's output gradient) only the band reads
+    _SPLIT_DECONV = {2: ("conv3_1", 8), 3: ("conv4_1", 16)}      # K: (the layer whose output gradient leads cat(K+1), its level stride)
+
+    def _attach_unread(self, band, origin):
+        """The launches of `backward(skip_unread=True)`: gradients whose only reader is a banded or windowed launch are produced
+        where that reader looks.  (a) deconv2 / deconv3's data gradient as two launches over slices of one weight: the columns of
+        conv3_1's / conv4_1's output gradient (`add` of bwd_band["conv4"] / ["conv5"]) on the band's rows, the rest (deconv3's /
+        deconv4's segment, read in full by the next deconvolution's gradient) on every row; (b) conv3_1 / conv_redir on the
+        correlation-reach band (`band.corr_width` pixels from `band.win[:, 2]`: what the window's correlation adjoint reads), their
+        input still masked to the wide band, on which gz_cat3 exists.  The wide forms stay in `bwd_band_wide`."""
+        B = self.B
+
+        def planned(name, wi, x, c0, rows, out_hw, kw):
+            M = B * rows[0] * rows[1]
+            pk = [len(t) * wi.KC for _, _, t in wi.phases]
+            kw.setdefault("variant", self._variant_for(wi))       # (a narrower band of a planned layer keeps that plan's form)
+            bm, target = self._tile_rows_and_slots(wi, kw)
+            S = ig.splitk_for(M, wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target)
+            kw["variant"], S = ig.tuned(wi, M, kw, kw["variant"], S, rows=rows)
+            if len(wi.phases) * S * M * wi.Npad > self.ws.numel():
+                S = 1
+            self._band_plans[name] = (wi, x, c0, rows, out_hw, kw)
+            return ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
+
+        for k, (lead, ls) in self._SPLIT_DECONV.items():
+            src, chunk0, _, Gd, _, rows = self.tail_args[k]
+            w = self._conv(f"deconv{k}").weight
+            main, n_band = w.shape[0] - 2, self._conv(lead).out_channels
+            if n_band % 32 or not 0 < n_band < main:
+                continue
+            name = f"deconv{k}"
+            if name not in self._split_w:        # packed once for the engine's life: a step's captured graphs point into them
+                self._split_w[name] = (ig.deconv_backward_weights(w[:n_band], 1), ig.deconv_backward_weights(w[n_band:main], 1))
+            w_band, w_rest = self._split_w[name]
+            self.bwd_band[name] = planned(name, w_band, src, chunk0, (rows[0], band.width // ls), rows,
+                                          dict(out_f32=Gd, out_f32_chunk0=0, row_band=(origin, 8, ls)))
+            self.bwd_rest[name + " rest"] = planned(name + " rest", w_rest, src, chunk0, rows, rows,
+                                                    dict(out_f32=Gd, out_f32_chunk0=n_band // 32))
+            self._pf_band[k + 1] = (n_band // 32, ls)
+        cw = int(getattr(band, "corr_width", 0))
+        if cw:
+            if cw % 8 or cw > band.width:
+                raise ValueError("correlation band: a multiple of 8 pixels inside the band")
+            for name in ("conv3_1", "conv_redir"):
+                wi, x, c0, rows, out_hw, _, kw = self._plans[("bwd", name)]
+                self.bwd_band_wide[name] = self.bwd_band[name]
+                kw = dict(kw, row_band=(band.win[:, 2], 8, 8), in_band=(origin, 8, 8, band.width // 8))
+                self.bwd_band[name] = planned(name, wi, x, c0, (rows[0], cw // 8), out_hw, kw)
 
     def replan(self, kind: str, name: str, tag: str):
         """(weights, input planes, first chunk, row grid, output grid, make_launch kwargs) of a prepared launch, band geometry
         included: tools/sweep_igemm_launches.py rebuilds it with other kernel forms / split-K factors."""
+        if kind == "bwd" and name in self._band_plans and tag == ("full" if name in self.bwd_rest else "band"):
+            wi, x, c0, rows, out_hw, kw = self._band_plans[name]          # (the launches of `_attach_unread`)
+            return wi, x, c0, rows, out_hw, dict(kw)
         wi, x, c0, rows, out_hw, _, kw = self._plans[(kind, name)]
         kw = dict(kw)
         if tag == "band":
@@ -532,9 +588,11 @@ class FlowNetCHeadEngine:
         [(name, 'fwd' | 'bwd', 'full' | 'band', launch, GFLOP)]."""
         rows = []
         for kind, table, tag in (("fwd", self.fwd, "full"), ("bwd", self.bwd, "full"), ("fwd", self.fwd_band, "band"),
-                                 ("bwd", self.bwd_band, "band")):
+                                 ("bwd", self.bwd_band, "band"), ("bwd", self.bwd_rest, "full")):
             for name, launch in table.items():
-                wi = self._plans[(kind, name)][0]
+                # (a launch of `_attach_unread` has weights of its own: a slice of the layer's)
+                wi = self._band_plans[name][0] if kind == "bwd" and table is not self.bwd and name in self._band_plans else \
+                    self._plans[(kind, name)][0]
                 d = launch.desc
                 rows.append((name, kind, tag, launch, wi.flops(d.B * d.Hr * d.Wr) / 1e9))
         if self._prefix is not None:           # full-frame conv1-3 of the first / second frames, once per attack() call
@@ -579,10 +637,23 @@ class FlowNetCHeadEngine:
                                                           self.pf_wm[k].shape[0], L.ptr(self.pf_b[k]), L.ptr(self.flow[k]), self.B, src.H, src.W,
                                                           L.stream()), "predict_flow forward (mfma)")
 
-    def _pf_backward(self, k, gy, accumulate, finalize=None):
+    def _pf_backward(self, k, gy, accumulate, finalize=None, region=None):
         """predict_flowK^T; `finalize` = (activation planes, gradient planes, first chunk, chunks) of the segment whose gradient
-        sum is complete with this launch (deconvK's output): x LeakyReLU' -> planes in the same kernel (round 4)."""
+        sum is complete with this launch (deconvK's output): x LeakyReLU' -> planes in the same kernel (round 4).
+        `region` = (head chunks, kind, origin table, ints per pair, divisor, rows, columns, margin, window GradSum | None): the
+        leading chunks are read on that region only and are written there only (ufr_flow_head_planes_backward_regions)."""
         src, chunks = self.pf_src[k]
+        if region is not None:
+            head, kind, origin, stride, div, rh, rw, margin, wout = region
+            act, out, c0, n = finalize if finalize is not None else (None, None, 0, 0)
+            L.check(L.lib().ufr_flow_head_planes_backward_regions(
+                L.ptr(gy), L.ptr(self.pf_w[k]), self.pf_w[k].shape[0], L.ptr(self.pf_G[k].t), self.pf_G[k].chunks, 0, chunks, self.B,
+                src.H, src.W, int(accumulate), int(head), int(kind), L.ptr(origin), int(stride), int(div), int(rh), int(rw), int(margin),
+                L.ptr(wout.t) if wout is not None else None, wout.B if wout is not None else 0,
+                L.ptr(act.t) if act is not None else None, L.ptr(out.t) if out is not None else None,
+                out.plane_stride if out is not None else 0, int(c0), int(n), float(ig.LEAKY), L.stream()),
+                "predict_flow backward (regions)")
+            return
         if finalize is not None:
             act, out, c0, n = finalize
             L.check(L.lib().ufr_flow_head_planes_backward_finalize(L.ptr(gy), L.ptr(self.pf_w[k]), self.pf_w[k].shape[0], L.ptr(self.pf_G[k].t),
@@ -684,12 +755,16 @@ class FlowNetCHeadEngine:
             self._pf_forward(k)
         return self.flow[2]
 
-    def backward(self, g_flow2: torch.Tensor, band=None, fused_window: bool = True):
+    def backward(self, g_flow2: torch.Tensor, band=None, fused_window: bool = True, skip_unread: bool = True):
         """d loss / d flow2 -> (d/d conv2a, d/d conv3a, d/d conv3b), all NCHW float32 (static buffers).
         With a band: the data gradients of conv5, conv4_1, conv4, conv3_1 and conv_redir run on the band's columns and the
         correlation's adjoint on the window's cells (only those are read behind a windowed prefix).  When the band carries
         `g3_window` (the window-sized gradient of conv3, both frames: patch_attack.py) and `fused_window`, the correlation's
-        adjoints are written there directly and the last two results are None."""
+        adjoints are written there directly and the last two results are None.
+        `skip_unread` (with a band and `fused_window`): gradients that only a banded or windowed launch reads are produced where
+        it reads them (`_attach_unread`; predict_flow2's conv2 chunks straight into the window prefix's addend when that prefix
+        runs on the engine) -- G_cat2[0:4] is then not written, G_cat3[0:8], G_cat4[0:16], G_in31 and G_c3a outside those regions
+        keep stale values.  False: every gradient sum in full, as the autograd Function and the training path need them."""
         L.require_hip(g_flow2, "g_flow2")
         B = self.B
         banded = band is not None and bool(band.width)
@@ -703,21 +778,35 @@ class FlowNetCHeadEngine:
         # `grad_finalize` launch per level (UFR_FUSE_FINALIZE=0: the separate launches)
         fuse = os.environ.get("UFR_FUSE_FINALIZE", "1") != "0"
         fin = lambda k: (gz[k][1], gz[k][2], gz[k][3], gz[k][4]) if fuse else None
-        self._pf_backward(2, g_flow2, accumulate=False, finalize=fin(2))
         eng_window = bool(fused_window and band is not None and getattr(band, "eng_window", False)
                           and getattr(self, "_wprefix", None) is not None)
-        if eng_window:                           # the window prefix runs on the engine: its conv2 gradient stays chunk-major
-            self.window_gather_conv2_gradient(band.cone_win, band.g2_margin)
+        skip = bool(skip_unread and banded and fused_window and self.siamese)
+        if skip and eng_window:                  # conv2's chunks on the window's cells, straight into conv3's addend: no gather
+            P = self._wprefix
+            wh, ww = P["hw"]
+            self._pf_backward(2, g_flow2, accumulate=False, finalize=fin(2),
+                              region=(4, L.UFR_PF_REGION_WINDOW, band.cone_win, 8, 4, wh // 4, ww // 4, band.g2_margin, P["G_gw2"]))
         else:
-            self.G_cat2.to_nchw(128, 0, out=self.g_c2a)
+            self._pf_backward(2, g_flow2, accumulate=False, finalize=fin(2))
+            if eng_window:                       # the window prefix runs on the engine: its conv2 gradient stays chunk-major
+                self.window_gather_conv2_gradient(band.cone_win, band.g2_margin)
+            else:
+                self.G_cat2.to_nchw(128, 0, out=self.g_c2a)
         for k in (2, 3, 4):
             Gs, act, out, chunk0, chunks = gz[k]
             if not fuse:
                 self._finalize(Gs, act, out, chunk0, chunks)      # LeakyReLU' of deconvK's output
             self._up_backward(k + 1)                               # -> d/d flow(K+1)
-            self.bwd[f"deconv{k}"]()                               # writes the gradient sum of cat(K+1)
+            region = None
+            if skip and k + 1 in self._pf_band:                    # cat(K+1)'s leading chunks: only the band is read
+                self.bwd_band[f"deconv{k}"]()
+                self.bwd_rest[f"deconv{k} rest"]()
+                head, ls = self._pf_band[k + 1]
+                region = (head, L.UFR_PF_REGION_BAND, band.win[:, 1], 8, ls, self.grid[ls][0], band.width // ls, 0, None)
+            else:
+                self.bwd[f"deconv{k}"]()                           # writes the gradient sum of cat(K+1)
             self._deconv_tail(k)
-            self._pf_backward(k + 1, self.g_flow[k + 1], accumulate=True, finalize=fin(k + 1))
+            self._pf_backward(k + 1, self.g_flow[k + 1], accumulate=True, finalize=fin(k + 1), region=region)
         Gs, act, out, chunk0, chunks = gz[5]
         if not fuse:
             self._finalize(Gs, act, out, chunk0, chunks)
@@ -731,7 +820,10 @@ class FlowNetCHeadEngine:
             self.G_in31.to_nchw(256, 0, out=self.g_c3a)
             return self.g_c2a, self.g_c3a, None
         for name in ("conv5", "conv4_1", "conv4", "conv3_1", "conv_redir"):
-            (self.bwd_band if banded else self.bwd)[name]()
+            if banded and not skip and name in self.bwd_band_wide:
+                self.bwd_band_wide[name]()
+            else:
+                (self.bwd_band if banded else self.bwd)[name]()
         # conv_redir's input and the correlation's two inputs
         gw = getattr(band, "g3_window", None) if (band is not None and fused_window) else None
         h8, w8 = self.grid[8]

@@ -80,9 +80,12 @@ class PatchAttackStep:
 
     def __init__(self, flow_net, args, batch, height, width, device="cuda:0", shared_patch=True,
                  exchange: ShardedExchange | None = None, use_graph=True, warmup=3, use_cone=None, patch_hw=None,
-                 sum_groups=1):
+                 sum_groups=1, skip_unread=True):
         L.lib()   # fail loudly, now, if libufr_hip.so is missing
         self.net, self.args = flow_net, args
+        # the engine's banded backward writes gradients that only the band / the window reads where they are read
+        # (flownetc_engine.py `backward`); False: every gradient sum in full
+        self.skip_unread = bool(skip_unread)
         self.B, self.H, self.W = batch, height, width
         self.dev = torch.device(device)
         self.shared = shared_patch
@@ -259,13 +262,15 @@ class PatchAttackStep:
         # column band for the head's most expensive data gradients (band_conv.py)
         self.band, reach = None, getattr(self.net, "BAND_REACH", None)
         if reach is not None and os.environ.get("UFR_BAND", "1") != "0":
-            from .band_conv import Band
+            from .band_conv import Band, corr_band_width
             bw = -(-(ww + 2 * reach + 31) // 32) * 32
             if W % 32 != 0 or bw * 4 > W * 3:
                 bw = 0                         # frame too narrow for a band: only the correlation's adjoint is windowed
             self._band_reach = reach
             self.band = Band(torch.zeros(B, 8, dtype=torch.int32, device=self.dev), bw, cone_win=self.win,
                              cone_hw=(wh, ww))
+            if bw and corr_band_width(ww) <= bw:   # conv3_1's / conv_redir's data gradients: the correlation's reach is enough
+                self.band.corr_width = corr_band_width(ww)
             if bw and os.environ.get("UFR_INCREMENTAL", "1") != "0":
                 self.band.inc_layers = tuple(getattr(self.net, "INCREMENTAL_LAYERS", ()))
 
@@ -289,6 +294,9 @@ class PatchAttackStep:
         if self.band is not None and self.band.width:   # band start: 32-pixel aligned, `reach` left of the window, inside the frame
             start = torch.div(self.win[:, 1] - self._band_reach, 32, rounding_mode="floor") * 32
             self.band.win[:, 1] = start.clamp(0, self.W - self.band.width)
+            if self.band.corr_width:
+                from .band_conv import corr_band_origin
+                self.band.win[:, 2] = corr_band_origin(self.win[:, 1], self.band.corr_width, self.W)
         if self.eng is not None:
             if prefix_features is not None:
                 self.eng.load_prefix_features(*prefix_features)
@@ -346,7 +354,7 @@ class PatchAttackStep:
                 if self.band is not None:        # the engine writes conv3's window gradient itself (fused correlation adjoint)
                     self.band.g3_window, self.band.g3_margin = gw3, m3
                     self.band.eng_window, self.band.g2_margin = True, m2
-                g2a, g3a, g3b = self.eng.backward(g_flow2.contiguous(), self.band)
+                g2a, g3a, g3b = self.eng.backward(g_flow2.contiguous(), self.band, skip_unread=self.skip_unread)
                 if g2a is not None:
                     self._win_copy(lib.ufr_window_gather, g2a, gw2, B, 128, H // ls2, W // ls2, ls2, m2)
                 if g3a is not None:

@@ -282,3 +282,69 @@ def test_graft_entry_build_runs():
     check) must pass in the build container."""
     import __graft_entry__ as g
     g.build()
+
+
+def _update_and_norm_entries():
+    """(entry, its message, a well-formed argument list, [(argument index, refused value)]) for every entry of csrc/raft_update.hip
+    and csrc/raft_norm.hip.  The well-formed list itself is never called: only copies with ONE argument replaced are."""
+    p, M, ps = ctypes.c_void_p(4096), 35, 8 * 35 * 32
+    return [
+        ("ufr_raft_flow_patches", b"raft flow patches", [p, p, ps, 1, 1, 5, 7, None],
+         [(0, None), (1, None), (2, 0), (2, -ps), (3, -1), (4, 0), (5, 0), (6, -1)]),
+        ("ufr_raft_motion_finish", b"raft motion finish", [p, ps, p, ps, 2, p, 1, 5, 7, None],
+         [(0, None), (2, None), (5, None), (1, 0), (3, 0), (3, -ps), (4, -1), (6, 0), (7, 0), (8, 0)]),
+        ("ufr_raft_motion_finish_slabs", b"raft motion finish (slabs)", [p, 3, 128, 126, p, 0.0, p, ps, p, ps, 2, p, 1, 5, 7, None],
+         [(0, None), (4, None), (6, None), (8, None), (11, None), (1, 0), (2, 256), (2, 120), (3, 127), (3, 0), (7, 0), (9, -1), (10, -1),
+          (12, 0), (13, 0), (14, 0)]),
+        ("ufr_raft_coords_step", b"raft coords step", [p, p, p, p, p, 70, None], [(0, None), (2, None), (3, None), (4, None), (5, 0), (5, -8)]),
+        ("ufr_grad_finalize_consume", b"grad finalize (consume)", [p, p, p, ps, M, 4, 0.0, None],
+         [(0, None), (1, None), (2, None), (3, 0), (3, -ps), (4, 0), (5, 0), (5, -1)]),
+        ("ufr_gru_gates_cm_forward", b"gru gates (chunk-major) forward", [p, p, ps, 1, p, ps, 2, M, 4, None],
+         [(0, None), (1, None), (4, None), (2, 0), (5, 0), (3, -1), (6, -1), (7, 0), (7, -M), (8, 0)]),
+        ("ufr_gru_gates_cm_forward_slabs", b"gru gates (chunk-major, from slabs) forward", [p, 3, 256, p, p, p, p, ps, 1, p, ps, 2, M, 4, None],
+         [(0, None), (3, None), (5, None), (6, None), (9, None), (1, 0), (2, 248), (2, 128), (2, 260), (7, 0), (10, -1), (8, -1), (11, -1),
+          (12, 0), (13, 0)]),
+        ("ufr_gru_blend_cm_forward", b"gru blend (chunk-major) forward", [p, p, p, ps, 1, p, ps, 2, M, 4, None],
+         [(0, None), (1, None), (2, None), (5, None), (3, 0), (6, 0), (4, -1), (7, -1), (8, 0), (9, 0)]),
+        ("ufr_gru_blend_cm_forward_slabs", b"gru blend (chunk-major, from slabs) forward", [p, 3, 128, p, p, p, p, p, ps, 1, p, ps, 2, M, 4, None],
+         [(0, None), (3, None), (5, None), (6, None), (7, None), (10, None), (1, 0), (2, 120), (2, 96), (2, 132), (8, 0), (11, -ps), (9, -1),
+          (12, -1), (13, 0), (14, 0)]),
+        ("ufr_gru_blend_cm_backward", b"gru blend (chunk-major) backward", [p, p, p, ps, 1, p, p, ps, 2, p, p, M, 4, p, None],
+         [(0, None), (1, None), (2, None), (5, None), (6, None), (9, None), (10, None), (3, 0), (7, 0), (4, -1), (8, -1), (11, 0), (12, 0)]),
+        ("ufr_gru_gates_cm_backward", b"gru gates (chunk-major) backward", [p, p, ps, 1, p, p, p, ps, 2, p, M, 4, 1, p, None],
+         [(0, None), (1, None), (4, None), (5, None), (6, None), (9, None), (2, 0), (7, 0), (3, -1), (8, -1), (10, 0), (11, 0)]),
+        ("ufr_cm_norm_stats", b"norm stats", [p, p, p, M, 1, 4, 1e-5, None], [(0, None), (1, None), (2, None), (3, 0), (4, 0), (5, 0)]),
+        ("ufr_cm_norm_stats_apply", b"norm stats + apply", [p, p, p, 1e-5, p, ps, 1, p, ps, 2, M, 1, 4, 1, 1, None],
+         [(0, None), (1, None), (2, None), (7, None), (5, 0), (6, -1), (8, 0), (8, -ps), (9, -1), (10, 0), (11, 0), (12, 0)]),
+        ("ufr_cm_norm_apply", b"norm apply", [p, p, p, ps, 1, p, ps, 2, M, 1, 4, 1, 1, None],
+         [(0, None), (5, None), (3, 0), (4, -1), (6, 0), (7, -1), (8, 0), (9, 0), (10, 0)]),
+        ("ufr_cm_norm_backward", b"norm backward", [p, p, p, 1, p, p, p, p, ps, 2, M, 1, 4, 1, None],
+         [(0, None), (1, None), (7, None), (3, -1), (8, 0), (9, -1), (10, 0), (11, 0), (12, 0)]),
+        ("ufr_cm_masked_copy", b"masked copy", [p, p, 64, p, 1024, None], [(0, None), (1, None), (3, None), (2, -8), (4, 0), (4, 1020), (4, -8)]),
+    ]
+
+
+def test_update_block_and_norm_entries_refuse_bad_arguments_before_any_launch():
+    """Every entry of csrc/raft_update.hip and csrc/raft_norm.hip checks its arguments before its first HIP call: null pointers,
+    empty extents, a split count below 1, a slab row stride that does not hold the columns read (or is no multiple of the 8-wide
+    accesses), an element count the 8-wide masked copy cannot walk, and -- like `ufr_raft_flow_patches` always did -- plane strides
+    that are not positive and negative chunk offsets.  Each is refused with -1 and the entry's own message; the pointers are never
+    dereferenced, so this runs without a GPU."""
+    from understanding_flow_robustness_amd import _lib as L
+    lib = L.lib()
+    entries = _update_and_norm_entries()
+    assert len(entries) == 16
+    for name, message, good, bad in entries:
+        assert len(good) == len(L.SIGNATURES[name])
+        for index, value in bad:
+            args = list(good)
+            args[index] = value
+            lib.ufr_corr_forward(None, None, None, 0, 1, 1, 4, 4, None, None)          # another message in the channel first
+            rc = getattr(lib, name)(*args)
+            assert rc == -1, f"{name}: argument {index} = {value!r} was accepted (rc {rc})"
+            assert lib.ufr_last_error().startswith(message + b":"), (name, index, value, lib.ufr_last_error())
+    # the statistics form of the norm adjoint needs its sums and its workspace
+    p, M, ps = ctypes.c_void_p(4096), 35, 8 * 35 * 32
+    for sums, ws in ((None, p), (p, None), (None, None)):
+        assert lib.ufr_cm_norm_backward(p, p, p, 1, p, sums, ws, p, ps, 2, M, 1, 4, 1, None) == -1
+        assert b"the statistics form needs sums and a workspace" in lib.ufr_last_error()

@@ -347,7 +347,9 @@ extern "C" int ufr_cm_norm_stats(const float* x, float* stats, double* workspace
 extern "C" int ufr_cm_norm_stats_apply(const float* x, float* stats, double* workspace, float eps, const void* res,
                                        long res_plane_stride, int res_chunk0, void* out, long out_plane_stride, int out_chunk0, long HW,
                                        int n, int chunks, int relu1, int relu2, ufr_stream_t stream) {
-  UFR_REQUIRE(x && stats && workspace && out && HW > 0 && n > 0 && chunks > 0, "norm stats + apply: bad argument");
+  UFR_REQUIRE(x && stats && workspace && out && HW > 0 && n > 0 && chunks > 0 && out_plane_stride > 0 && out_chunk0 >= 0 &&
+                  (!res || (res_plane_stride > 0 && res_chunk0 >= 0)),
+              "norm stats + apply: bad argument");
   const int S = slices_for(HW, n, chunks);
   hipStream_t st = ufr::as_stream(stream);
   cm_sums_kernel<0><<<dim3(S, n, chunks), 256, 0, st>>>(x, nullptr, nullptr, 0, nullptr, workspace, HW, n, chunks, 0);
@@ -362,7 +364,9 @@ extern "C" int ufr_cm_norm_stats_apply(const float* x, float* stats, double* wor
 extern "C" int ufr_cm_norm_apply(const float* x, const float* stats, const void* res, long res_plane_stride, int res_chunk0, void* out,
                                  long out_plane_stride, int out_chunk0, long HW, int n, int chunks, int relu1, int relu2,
                                  ufr_stream_t stream) {
-  UFR_REQUIRE(x && out && HW > 0 && n > 0 && chunks > 0, "norm apply: bad argument");
+  UFR_REQUIRE(x && out && HW > 0 && n > 0 && chunks > 0 && out_plane_stride > 0 && out_chunk0 >= 0 &&
+                  (!res || (res_plane_stride > 0 && res_chunk0 >= 0)),
+              "norm apply: bad argument");
   const long total = (long)chunks * n * HW * 4;
   cm_norm_apply_kernel<<<ufr::stream_grid(total, 256), 256, 0, ufr::as_stream(stream)>>>(
       x, stats, static_cast<const __bf16*>(res), res_plane_stride, res_chunk0, static_cast<__bf16*>(out), out_plane_stride, out_chunk0, HW, n,
@@ -373,7 +377,8 @@ extern "C" int ufr_cm_norm_apply(const float* x, const float* stats, const void*
 extern "C" int ufr_cm_norm_backward(const float* x, const float* G, const void* outmask, int mask_chunk0, const float* stats,
                                     float* sums, double* workspace, void* gz, long gz_plane_stride, int gz_chunk0, long HW, int n,
                                     int chunks, int relu1, ufr_stream_t stream) {
-  UFR_REQUIRE(x && G && gz && HW > 0 && n > 0 && chunks > 0, "norm backward: bad argument");
+  UFR_REQUIRE(x && G && gz && HW > 0 && n > 0 && chunks > 0 && gz_plane_stride > 0 && gz_chunk0 >= 0 && (!outmask || mask_chunk0 >= 0),
+              "norm backward: bad argument");
   UFR_REQUIRE(!stats || (sums && workspace), "norm backward: the statistics form needs sums and a workspace");
   hipStream_t st = ufr::as_stream(stream);
   if (stats) {
@@ -396,7 +401,8 @@ extern "C" int ufr_cm_norm_backward(const float* x, const float* G, const void* 
 
 extern "C" int ufr_cm_masked_copy(const float* G, const void* outmask, long mask_elem_offset, float* out, long elems,
                                   ufr_stream_t stream) {
-  UFR_REQUIRE(G && outmask && out && elems > 0 && elems % 8 == 0, "masked copy: bad argument");
+  UFR_REQUIRE(G && outmask && out && elems > 0 && elems % 8 == 0 && mask_elem_offset >= 0,
+              "masked copy: bad argument");
   cm_masked_copy_kernel<<<ufr::stream_grid(elems / 8, 256), 256, 0, ufr::as_stream(stream)>>>(
       G, static_cast<const __bf16*>(outmask) + mask_elem_offset, 0, out, elems / 8);
   return ufr::launched("cm_masked_copy_kernel");

@@ -375,7 +375,8 @@ extern "C" int ufr_raft_flow_patches(const float* flow, void* planes, long plane
 
 extern "C" int ufr_raft_motion_finish(void* p1, long plane_stride1, void* p2, long plane_stride2, int chunk0, const float* flow, int B,
                                       int H, int W, ufr_stream_t stream) {
-  UFR_REQUIRE(p1 && p2 && flow && B > 0 && H > 0 && W > 0 && chunk0 >= 0, "raft motion finish: bad argument");
+  UFR_REQUIRE(p1 && p2 && flow && B > 0 && H > 0 && W > 0 && chunk0 >= 0 && plane_stride1 > 0 && plane_stride2 > 0,
+              "raft motion finish: bad argument");
   const long M = (long)B * H * W;
   motion_finish_kernel<<<ufr::stream_grid(M * 16, 256), 256, 0, ufr::as_stream(stream)>>>(
       static_cast<__bf16*>(p1), plane_stride1, static_cast<__bf16*>(p2), plane_stride2, chunk0, flow, M, (long)H * W);
@@ -385,7 +386,8 @@ extern "C" int ufr_raft_motion_finish(void* p1, long plane_stride1, void* p2, lo
 extern "C" int ufr_raft_motion_finish_slabs(const float* ws, int splitk, int Npad, int N, const float* bias, float slope, void* p1,
                                             long plane_stride1, void* p2, long plane_stride2, int chunk0, const float* flow, int B, int H,
                                             int W, ufr_stream_t stream) {
-  UFR_REQUIRE(ws && bias && p1 && p2 && flow && B > 0 && H > 0 && W > 0 && chunk0 >= 0 && splitk >= 1 && Npad == 128 && N > 0 && N <= 126,
+  UFR_REQUIRE(ws && bias && p1 && p2 && flow && B > 0 && H > 0 && W > 0 && chunk0 >= 0 && splitk >= 1 && Npad == 128 && N > 0 && N <= 126 &&
+                  plane_stride1 > 0 && plane_stride2 > 0,
               "raft motion finish (slabs): bad argument");
   const long M = (long)B * H * W;
   motion_finish_slabs_kernel<<<ufr::stream_grid(M * 16, 256), 256, 0, ufr::as_stream(stream)>>>(
@@ -396,7 +398,8 @@ extern "C" int ufr_raft_motion_finish_slabs(const float* ws, int splitk, int Npa
 
 extern "C" int ufr_gru_gates_cm_forward(float* zr, const void* h, long h_plane_stride, int h_chunk0, void* rh, long rh_plane_stride,
                                         int rh_chunk0, long M, int chunks, ufr_stream_t stream) {
-  UFR_REQUIRE(zr && h && rh && M > 0 && chunks > 0, "gru gates (chunk-major) forward: bad argument");
+  UFR_REQUIRE(zr && h && rh && M > 0 && chunks > 0 && h_plane_stride > 0 && rh_plane_stride > 0 && h_chunk0 >= 0 && rh_chunk0 >= 0,
+              "gru gates (chunk-major) forward: bad argument");
   gates_fwd_kernel<<<ufr::stream_grid((long)chunks * M * 4, 256), 256, 0, ufr::as_stream(stream)>>>(
       zr, static_cast<const __bf16*>(h), h_plane_stride, h_chunk0, static_cast<__bf16*>(rh), rh_plane_stride, rh_chunk0, M, chunks,
       SlabSrc{nullptr, nullptr, 0, 0, 0, nullptr});
@@ -406,7 +409,8 @@ extern "C" int ufr_gru_gates_cm_forward(float* zr, const void* h, long h_plane_s
 extern "C" int ufr_gru_gates_cm_forward_slabs(const float* ws, int splitk, int Npad, const float* bias, const float* addend, float* zr, const void* h,
                                               long h_plane_stride, int h_chunk0, void* rh, long rh_plane_stride, int rh_chunk0, long M,
                                               int chunks, ufr_stream_t stream) {
-  UFR_REQUIRE(ws && bias && zr && h && rh && M > 0 && chunks > 0 && splitk >= 1 && Npad >= 2 * chunks * 32 && Npad % 8 == 0,
+  UFR_REQUIRE(ws && bias && zr && h && rh && M > 0 && chunks > 0 && splitk >= 1 && Npad >= 2 * chunks * 32 && Npad % 8 == 0 &&
+                  h_plane_stride > 0 && rh_plane_stride > 0 && h_chunk0 >= 0 && rh_chunk0 >= 0,
               "gru gates (chunk-major, from slabs) forward: bad argument");
   gates_fwd_kernel<<<ufr::stream_grid((long)chunks * M * 4, 256), 256, 0, ufr::as_stream(stream)>>>(
       zr, static_cast<const __bf16*>(h), h_plane_stride, h_chunk0, static_cast<__bf16*>(rh), rh_plane_stride, rh_chunk0, M, chunks,
@@ -416,7 +420,8 @@ extern "C" int ufr_gru_gates_cm_forward_slabs(const float* ws, int splitk, int N
 
 extern "C" int ufr_gru_blend_cm_forward(float* q, const float* z, const void* h, long h_plane_stride, int h_chunk0, void* out,
                                         long out_plane_stride, int out_chunk0, long M, int chunks, ufr_stream_t stream) {
-  UFR_REQUIRE(q && z && h && out && M > 0 && chunks > 0, "gru blend (chunk-major) forward: bad argument");
+  UFR_REQUIRE(q && z && h && out && M > 0 && chunks > 0 && h_plane_stride > 0 && out_plane_stride > 0 && h_chunk0 >= 0 && out_chunk0 >= 0,
+              "gru blend (chunk-major) forward: bad argument");
   blend_fwd_kernel<<<ufr::stream_grid((long)chunks * M * 4, 256), 256, 0, ufr::as_stream(stream)>>>(
       q, z, static_cast<const __bf16*>(h), h_plane_stride, h_chunk0, static_cast<__bf16*>(out), out_plane_stride, out_chunk0, M, chunks,
       SlabSrc{nullptr, nullptr, 0, 0, 0, nullptr});
@@ -426,7 +431,8 @@ extern "C" int ufr_gru_blend_cm_forward(float* q, const float* z, const void* h,
 extern "C" int ufr_gru_blend_cm_forward_slabs(const float* ws, int splitk, int Npad, const float* bias, const float* addend, float* q, const float* z,
                                               const void* h, long h_plane_stride, int h_chunk0, void* out, long out_plane_stride,
                                               int out_chunk0, long M, int chunks, ufr_stream_t stream) {
-  UFR_REQUIRE(ws && bias && q && z && h && out && M > 0 && chunks > 0 && splitk >= 1 && Npad >= chunks * 32 && Npad % 8 == 0,
+  UFR_REQUIRE(ws && bias && q && z && h && out && M > 0 && chunks > 0 && splitk >= 1 && Npad >= chunks * 32 && Npad % 8 == 0 &&
+                  h_plane_stride > 0 && out_plane_stride > 0 && h_chunk0 >= 0 && out_chunk0 >= 0,
               "gru blend (chunk-major, from slabs) forward: bad argument");
   blend_fwd_kernel<<<ufr::stream_grid((long)chunks * M * 4, 256), 256, 0, ufr::as_stream(stream)>>>(
       q, z, static_cast<const __bf16*>(h), h_plane_stride, h_chunk0, static_cast<__bf16*>(out), out_plane_stride, out_chunk0, M, chunks,
@@ -437,7 +443,9 @@ extern "C" int ufr_gru_blend_cm_forward_slabs(const float* ws, int splitk, int N
 extern "C" int ufr_gru_blend_cm_backward(const float* q, const float* z, const void* h, long h_plane_stride, int h_chunk0,
                                          const float* g, void* gq, long gq_plane_stride, int gq_chunk0, float* g_z, float* g_h, long M,
                                          int chunks, float* acc_gq, ufr_stream_t stream) {
-  UFR_REQUIRE(q && z && h && g && gq && g_z && g_h && M > 0 && chunks > 0, "gru blend (chunk-major) backward: bad argument");
+  UFR_REQUIRE(q && z && h && g && gq && g_z && g_h && M > 0 && chunks > 0 && h_plane_stride > 0 && gq_plane_stride > 0 && h_chunk0 >= 0 &&
+                  gq_chunk0 >= 0,
+              "gru blend (chunk-major) backward: bad argument");
   blend_bwd_kernel<<<ufr::stream_grid((long)chunks * M * 4, 256), 256, 0, ufr::as_stream(stream)>>>(
       q, z, static_cast<const __bf16*>(h), h_plane_stride, h_chunk0, g, static_cast<__bf16*>(gq), gq_plane_stride, gq_chunk0, g_z, g_h, M,
       chunks, acc_gq);
@@ -447,7 +455,9 @@ extern "C" int ufr_gru_blend_cm_backward(const float* q, const float* z, const v
 extern "C" int ufr_gru_gates_cm_backward(const float* zr, const void* h, long h_plane_stride, int h_chunk0, const float* g_z,
                                          float* g_rh, void* gzr, long gzr_plane_stride, int gzr_chunk0, float* g_h, long M,
                                          int chunks, int consume_g_rh, float* acc_gzr, ufr_stream_t stream) {
-  UFR_REQUIRE(zr && h && g_z && g_rh && gzr && g_h && M > 0 && chunks > 0, "gru gates (chunk-major) backward: bad argument");
+  UFR_REQUIRE(zr && h && g_z && g_rh && gzr && g_h && M > 0 && chunks > 0 && h_plane_stride > 0 && gzr_plane_stride > 0 && h_chunk0 >= 0 &&
+                  gzr_chunk0 >= 0,
+              "gru gates (chunk-major) backward: bad argument");
   gates_bwd_kernel<<<ufr::stream_grid((long)chunks * M * 4, 256), 256, 0, ufr::as_stream(stream)>>>(
       zr, static_cast<const __bf16*>(h), h_plane_stride, h_chunk0, g_z, g_rh, static_cast<__bf16*>(gzr), gzr_plane_stride, gzr_chunk0, g_h,
       M, chunks, consume_g_rh, acc_gzr);

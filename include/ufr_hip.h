@@ -270,6 +270,26 @@ int ufr_patch_paste_placed(const float* tgt, const float* ref, const float* patc
 int ufr_patch_paste_placed_rect(const float* tgt, const float* ref, const float* patch_p, const float* mask_p,
                                 const int* origins, float* adv_tgt, float* adv_ref, int B, int H, int W, int ph, int pw,
                                 int do_clamp, float lo, float hi, const float* gate_state, ufr_stream_t stream);
+/* Loading one attack() call of a patch-coordinate step, the frame half: the caller's frames are read once and leave as the step's
+ * copies (tgt_dst / ref_dst) and as the first, un-clamped paste (adv_tgt / adv_ref = ufr_patch_paste_placed with do_clamp = 0 on
+ * patch_p / mask_p / origins, which ufr_attack_place has written on the same stream).  16-byte accesses when W % 4 == 0 and every
+ * frame pointer is 16-byte aligned. */
+int ufr_attack_load_frames(const float* tgt, const float* ref, const float* patch_p, const float* mask_p, const int* origins,
+                           float* tgt_dst, float* ref_dst, float* adv_tgt, float* adv_ref, int B, int H, int W, int ph, int pw,
+                           ufr_stream_t stream);
+/* The canvas masks M_b alone (the mask_out of ufr_patch_paste_placed, nothing else written). */
+int ufr_patch_mask_placed(const float* mask_p, const int* origins, float* mask_out, int B, int H, int W, int ph, int pw,
+                          ufr_stream_t stream);
+/* ufr_conv1_unpack_grad + ufr_patch_grad_crop_window in one launch: the crop reads conv1's packed gradient sum
+ * G [1][2B * (wh/2 + 3) * (ww/2 + 2)][32] through the unpacking's index map; same rows, bit for bit. */
+int ufr_patch_grad_crop_packed(const float* G, const int* win, const float* mask_p, const int* origins, const float* loss_local,
+                               float* rows, int B, int H, int W, int wh, int ww, int ph, int pw, int groups, ufr_stream_t stream);
+/* ufr_patch_apply + ufr_patch_paste_placed_rect in one launch (one thread per patch element: sum of the rows in ascending order,
+ * step, store, re-paste into every pair); a stopped step (gate_state[0] != 0) writes *loss only. */
+int ufr_patch_apply_paste_rect(const float* rows, int n_rows, float* patch_p, float* loss, const float* tgt, const float* ref,
+                               const float* mask_p, const int* origins, float* adv_tgt, float* adv_ref, int B, int H, int W, int ph,
+                               int pw, float step, float bound, int do_clamp, float lo, float hi, const float* gate_state,
+                               ufr_stream_t stream);
 /* ufr_flow_loss: loss = mean_b,h,w(1 - cos(flow, target))            (kind 0, main.py:564-566)
  *             or mean(sqrt(sum_c (flow-target)^2 + 1e-8))           (kind 1, main.py:557-562)
  *   flow,target: [B,2,H,W].  Writes d loss / d flow (already scaled by `weight`, = 1-alpha) to
@@ -497,6 +517,21 @@ int ufr_cone_window(const float* mask, int N, long mask_bstride, int C, int H, i
  * edges only) are written as 0.  scatter is the inverse and skips the rim. */
 int ufr_window_gather(const float* src, float* dst, const int* win, int n_win, int N, int C, int Hs, int Ws,
                       int wh, int ww, int level_stride, int margin, ufr_stream_t stream);
+/* Two ufr_window_gather calls (margin 0, level stride 1, one window per image) in one launch: xw [2N,C,wh,ww] = the windows of a
+ * [N,C,Hs,Ws], then of b; *zero (optional) = 0.f. */
+int ufr_window_gather_pair(const float* a, const float* b, float* xw, const int* win, float* zero, int N, int C, int Hs, int Ws,
+                           int wh, int ww, ufr_stream_t stream);
+/* Loading one attack() call of a patch-coordinate step, the placement half, in one launch of one workgroup: patch / mask_p /
+ * patch_init [3,ph,pw] and the origins [B,2] (`origins` on the device, or `origins_host`, validated here and handed over as a kernel
+ * argument up to 64 pairs; exactly one of the two) are copied to their *_dst (loaded_dst, optional, = patch too), state[0..3] = 0.
+ * With a chain: win = the table ufr_cone_window computes from the canvas masks (their box is origin + box(mask_p), clipped to the
+ * frame), state[3] = the number of pairs whose needed extent exceeds win_h x win_w, and, with band_win and band_width > 0,
+ * band_win[b][1] = clamp(floor((win[b][1] - band_reach) / 32) * 32, 0, W - band_width) and, with corr_width > 0,
+ * band_win[b][2] = clamp(win[b][1] - corr_reach, 0, W - corr_width). */
+int ufr_attack_place(const float* patch, const float* mask_p, const float* patch_init, const int* origins, const int* origins_host,
+                     float* patch_dst, float* mask_dst, float* init_dst, float* loaded_dst, int* origins_dst, float* state, int B,
+                     int H, int W, int ph, int pw, const ufr_cone_chain* chain, int win_h, int win_w, int* win, int* band_win,
+                     int band_width, int band_reach, int corr_width, int corr_reach, ufr_stream_t stream);
 int ufr_window_scatter(const float* src, float* dst, const int* win, int n_win, int N, int C, int Hd, int Wd,
                        int wh, int ww, int level_stride, int margin, ufr_stream_t stream);
 
@@ -716,6 +751,13 @@ int ufr_nchw_to_planes(const float* x, void* planes, long plane_stride, int chun
 int ufr_window_scatter_planes(const float* src, void* planes, long plane_stride, int chunk0, const int* win, int n_win,
                               int N, int C, int Hd, int Wd, int wh, int ww, int level_stride, int margin,
                               ufr_stream_t stream);
+/* FlowNetC's windowed conv2 (first frames, 128 channels at 1/4) and conv3 (both frames, 256 channels at 1/8) from their window
+ * planes (2B images each, chunk 0 on) into the head's buffers in one launch: cat2 chunks 0-3, c3a / c3b chunks 0-7 (B images each)
+ * and conv3's float32 value (p0 + p1) + p2 into c3_nchw [2B,256,H/8,W/8], all outside the inexact rim (m2 / m3 cells, the rule of
+ * ufr_window_scatter_planes); c3w_nchw [2B,256,wh/8,ww/8] receives every cell of the window's conv3.  H, W, wh, ww in pixels. */
+int ufr_window_features_planes(const void* c2w, long c2w_stride, const void* c3w, long c3w_stride, void* cat2, long cat2_stride,
+                               void* c3a, long c3a_stride, void* c3b, long c3b_stride, float* c3_nchw, float* c3w_nchw,
+                               const int* win, int B, int H, int W, int wh, int ww, int m2, int m3, ufr_stream_t stream);
 int ufr_chunks_to_nchw(const void* planes, long plane_stride, const float* f32, int chunk0, const void* mask,
                        int mask_chunk0, float* out, int B, int C, int H, int W, float scale, float slope,
                        ufr_stream_t stream);

@@ -247,6 +247,143 @@ __global__ void paste_placed_rect_kernel(const float* __restrict__ tgt, const fl
   }
 }
 
+// ---- one attack() call's frames in one pass (ufr_attack_load_frames) -------------------------------------------------------------
+// The caller's frames are read once: the step's own copies (tgt_dst / ref_dst) and the first, un-clamped paste of both (adv_tgt /
+// adv_ref, the arithmetic of paste_placed_kernel with do_clamp = 0) leave in the same pass.  V = 4: 16-byte accesses (W % 4 == 0 and
+// aligned pointers, checked by the host); V = 1 otherwise.
+__device__ __forceinline__ float paste_value(float img, float m, float pv) {
+  const float mp = m * pv, om = 1.0f - m;
+  return om * img + mp;
+}
+
+template <int V>
+__global__ void load_frames_kernel(const float* tgt, const float* ref, const float* __restrict__ patch_p,
+                                   const float* __restrict__ mask_p, const int* __restrict__ origins, float* tgt_dst, float* ref_dst,
+                                   float* __restrict__ adv_tgt, float* __restrict__ adv_ref, long total, int H, int W, int ph,
+                                   int pw) {
+  const long HW = (long)H * W;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long idx = q * V;
+    const long bc = idx / HW, pix = idx - bc * HW;
+    const int b = (int)(bc / 3), c = (int)(bc - 3L * b);
+    const int y = (int)(pix / W), x = (int)(pix - (long)y * W);
+    const int i = y - origins[2 * b], j0 = x - origins[2 * b + 1];
+    float t[V], r[V], a[V], d[V];
+    if constexpr (V == 4) {
+      const float4 tv = *reinterpret_cast<const float4*>(tgt + idx), rv = *reinterpret_cast<const float4*>(ref + idx);
+      t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+      r[0] = rv.x; r[1] = rv.y; r[2] = rv.z; r[3] = rv.w;
+    } else {
+      t[0] = tgt[idx];
+      r[0] = ref[idx];
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const int j = j0 + k;
+      float m = 0.f, pv = 0.f;
+      if ((unsigned)i < (unsigned)ph && (unsigned)j < (unsigned)pw) {
+        const int e = (c * ph + i) * pw + j;
+        m = mask_p[e];
+        pv = patch_p[e];
+      }
+      a[k] = paste_value(t[k], m, pv);
+      d[k] = paste_value(r[k], m, pv);
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(tgt_dst + idx) = make_float4(t[0], t[1], t[2], t[3]);
+      *reinterpret_cast<float4*>(ref_dst + idx) = make_float4(r[0], r[1], r[2], r[3]);
+      *reinterpret_cast<float4*>(adv_tgt + idx) = make_float4(a[0], a[1], a[2], a[3]);
+      *reinterpret_cast<float4*>(adv_ref + idx) = make_float4(d[0], d[1], d[2], d[3]);
+    } else {
+      tgt_dst[idx] = t[0];
+      ref_dst[idx] = r[0];
+      adv_tgt[idx] = a[0];
+      adv_ref[idx] = d[0];
+    }
+  }
+}
+
+// The canvas masks M_b = place(Mp, origin_b) alone (what paste_placed_kernel writes to mask_out): read rarely, so not on the load path.
+__global__ void mask_placed_kernel(const float* __restrict__ mask_p, const int* __restrict__ origins, float* __restrict__ mask_out,
+                                   long total, int H, int W, int ph, int pw) {
+  const long HW = (long)H * W;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const long bc = idx / HW, pix = idx - bc * HW;
+    const int b = (int)(bc / 3), c = (int)(bc - 3L * b);
+    const int y = (int)(pix / W), x = (int)(pix - (long)y * W);
+    const int i = y - origins[2 * b], j = x - origins[2 * b + 1];
+    mask_out[idx] = ((unsigned)i < (unsigned)ph && (unsigned)j < (unsigned)pw) ? mask_p[(c * ph + i) * pw + j] : 0.f;
+  }
+}
+
+// patch_grad_crop_window_kernel reading conv1's packed gradient sum G [1][2B * (wh/2 + 3) * (ww/2 + 2)][32] through the index map of
+// conv1_unpack_grad_kernel (plane_layout.hip): the window gradient of a pixel is G[(row + 2) * 32 + r] + G[(row + 1) * 32 + 12 + r],
+// the same two-term sum the unpacking stores -- the float32 window gradients are never written.
+__global__ void patch_grad_crop_packed_kernel(const float* __restrict__ G, const int* __restrict__ win,
+                                              const float* __restrict__ mask_p, const int* __restrict__ origins,
+                                              const float* __restrict__ loss_local, float* __restrict__ rows, int B, int H, int W,
+                                              int wh, int ww, int ph, int pw, int groups) {
+  const int n = 3 * ph * pw, per = B / groups;
+  const int Hp = (wh >> 1) + 3, Wp = (ww >> 1) + 2;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e <= n; e += gridDim.x * blockDim.x) {
+    if (e == n) {
+      for (int g = 0; g < groups; ++g) rows[(long)g * (n + 1) + n] = (g == 0) ? *loss_local : 0.f;
+      continue;
+    }
+    const int c = e / (ph * pw), r = e - c * ph * pw, i = r / pw, j = r - i * pw;
+    const bool shown = mask_p[e] != 0.f;
+    for (int g = 0; g < groups; ++g) {
+      float s = 0.f;
+      if (shown)
+        for (int b = g * per; b < (g + 1) * per; ++b) {
+          const int y = origins[2 * b] + i, x = origins[2 * b + 1] + j;
+          if ((unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) continue;
+          const int y0 = min(max(win[b * 8], 0), H - wh), x0 = min(max(win[b * 8 + 1], 0), W - ww);
+          const int wy = y - y0, wx = x - x0;
+          if ((unsigned)wy >= (unsigned)wh || (unsigned)wx >= (unsigned)ww) continue;     // zero gradient outside the window
+          const int k = (c * 2 + (wy & 1)) * 2 + (wx & 1);
+          const long ra = ((long)b * Hp + (wy >> 1) + 2) * Wp + (wx >> 1), rb = ra + (long)B * Hp * Wp;
+          const float ga = G[(ra + 2) * 32 + k] + G[(ra + 1) * 32 + 12 + k];
+          const float gb = G[(rb + 2) * 32 + k] + G[(rb + 1) * 32 + 12 + k];
+          s += ga + gb;
+        }
+      rows[(long)g * (n + 1) + e] = s;
+    }
+  }
+}
+
+// patch_apply_kernel + paste_placed_rect_kernel in one launch: the thread of patch element e adds the rows in ascending order, steps
+// and stores P[e], and re-pastes that element into every pair's frames (no other thread reads P[e]).  A stopped step (gate) writes
+// the loss only, as the two launches do.
+__global__ void patch_apply_paste_rect_kernel(const float* __restrict__ rows, int n_rows, float* __restrict__ patch_p,
+                                              float* __restrict__ loss, const float* __restrict__ tgt, const float* __restrict__ ref,
+                                              const float* __restrict__ mask_p, const int* __restrict__ origins,
+                                              float* __restrict__ adv_tgt, float* __restrict__ adv_ref, int B, int H, int W, int ph,
+                                              int pw, float step, float bound, int do_clamp, float lo, float hi,
+                                              const float* __restrict__ gate) {
+  const bool stopped = gate != nullptr && gate[0] != 0.f;
+  const int n = 3 * ph * pw;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e <= n; e += gridDim.x * blockDim.x) {
+    float s = 0.f;
+    for (int r = 0; r < n_rows; ++r) s += rows[(long)r * (n + 1) + e];
+    if (e == n) { *loss = s; continue; }                      // the gate reads it even for a void iteration
+    if (stopped) continue;
+    const float pv = patch_p[e] - clampf(step * s, -bound, bound);
+    patch_p[e] = pv;
+    const int c = e / (ph * pw), q = e - c * ph * pw, i = q / pw, j = q - i * pw;
+    const float m = mask_p[e], mp = m * pv, om = 1.0f - m;
+    for (int b = 0; b < B; ++b) {
+      const int y = origins[2 * b] + i, x = origins[2 * b + 1] + j;
+      if ((unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) continue;       // clipped like the full-canvas paste
+      const long o = ((long)b * 3 + c) * H * W + (long)y * W + x;
+      float a = om * tgt[o] + mp, d = om * ref[o] + mp;
+      if (do_clamp) { a = clampf(a, lo, hi); d = clampf(d, lo, hi); }
+      adv_tgt[o] = a;
+      adv_ref[o] = d;
+    }
+  }
+}
+
 // models/FlowNetC.py:73-79, :93-94 (`normalize_correctly`): the float64 mean subtraction of both frame stacks, written as
 // ONE float32 stack [Ba + Bb, C, H, W] (first frames, then second frames) -- replaces torch.cat + .double() + sub + .float().
 __global__ void normalize_frames_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out,
@@ -522,6 +659,62 @@ extern "C" int ufr_patch_paste_placed_rect(const float* tgt, const float* ref, c
   hipLaunchKernelGGL(paste_placed_rect_kernel, dim3(ufr::stream_grid(total, 256)), dim3(256), 0, ufr::as_stream(stream), tgt, ref,
                      patch_p, mask_p, origins, adv_tgt, adv_ref, B, H, W, ph, pw, do_clamp, lo, hi, gate_state);
   return ufr::launched("paste_placed_rect_kernel");
+}
+
+extern "C" int ufr_attack_load_frames(const float* tgt, const float* ref, const float* patch_p, const float* mask_p,
+                                      const int* origins, float* tgt_dst, float* ref_dst, float* adv_tgt, float* adv_ref, int B,
+                                      int H, int W, int ph, int pw, ufr_stream_t stream) {
+  UFR_REQUIRE(tgt && ref && patch_p && mask_p && origins && tgt_dst && ref_dst && adv_tgt && adv_ref,
+              "attack load frames: null pointer argument");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && ph > 0 && pw > 0 && ph <= H && pw <= W, "attack load frames: bad shape");
+  const long total = (long)B * 3 * H * W;
+  const uintptr_t bits = (uintptr_t)tgt | (uintptr_t)ref | (uintptr_t)tgt_dst | (uintptr_t)ref_dst | (uintptr_t)adv_tgt |
+                         (uintptr_t)adv_ref;
+  if (W % 4 == 0 && (bits & 15) == 0)
+    hipLaunchKernelGGL(load_frames_kernel<4>, dim3(ufr::stream_grid(total / 4, 256)), dim3(256), 0, ufr::as_stream(stream), tgt, ref,
+                       patch_p, mask_p, origins, tgt_dst, ref_dst, adv_tgt, adv_ref, total / 4, H, W, ph, pw);
+  else
+    hipLaunchKernelGGL(load_frames_kernel<1>, dim3(ufr::stream_grid(total, 256)), dim3(256), 0, ufr::as_stream(stream), tgt, ref,
+                       patch_p, mask_p, origins, tgt_dst, ref_dst, adv_tgt, adv_ref, total, H, W, ph, pw);
+  return ufr::launched("load_frames_kernel");
+}
+
+extern "C" int ufr_patch_mask_placed(const float* mask_p, const int* origins, float* mask_out, int B, int H, int W, int ph, int pw,
+                                     ufr_stream_t stream) {
+  UFR_REQUIRE(mask_p && origins && mask_out, "placed mask: null pointer argument");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && ph > 0 && pw > 0 && ph <= H && pw <= W, "placed mask: bad shape");
+  const long total = (long)B * 3 * H * W;
+  hipLaunchKernelGGL(mask_placed_kernel, dim3(ufr::stream_grid(total, 256)), dim3(256), 0, ufr::as_stream(stream), mask_p, origins,
+                     mask_out, total, H, W, ph, pw);
+  return ufr::launched("mask_placed_kernel");
+}
+
+extern "C" int ufr_patch_grad_crop_packed(const float* G, const int* win, const float* mask_p, const int* origins,
+                                          const float* loss_local, float* rows, int B, int H, int W, int wh, int ww, int ph, int pw,
+                                          int groups, ufr_stream_t stream) {
+  UFR_REQUIRE(G && win && mask_p && origins && loss_local && rows, "patch grad crop (packed): null pointer argument");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && ph > 0 && pw > 0 && ph <= H && pw <= W && wh > 0 && ww > 0 && wh <= H && ww <= W &&
+                  !(wh & 1) && !(ww & 1), "patch grad crop (packed): bad shape");
+  UFR_REQUIRE(groups > 0 && B % groups == 0, "patch grad crop (packed): the pairs must split evenly into %d groups", groups);
+  const int n = 3 * ph * pw + 1;
+  hipLaunchKernelGGL(patch_grad_crop_packed_kernel, dim3(ufr::ceil_div(n, 256)), dim3(256), 0, ufr::as_stream(stream), G, win,
+                     mask_p, origins, loss_local, rows, B, H, W, wh, ww, ph, pw, groups);
+  return ufr::launched("patch_grad_crop_packed_kernel");
+}
+
+extern "C" int ufr_patch_apply_paste_rect(const float* rows, int n_rows, float* patch_p, float* loss, const float* tgt,
+                                          const float* ref, const float* mask_p, const int* origins, float* adv_tgt, float* adv_ref,
+                                          int B, int H, int W, int ph, int pw, float step, float bound, int do_clamp, float lo,
+                                          float hi, const float* gate_state, ufr_stream_t stream) {
+  UFR_REQUIRE(rows && patch_p && loss && tgt && ref && mask_p && origins && adv_tgt && adv_ref,
+              "patch apply + rect paste: null pointer argument");
+  UFR_REQUIRE(n_rows > 0 && B > 0 && H > 0 && W > 0 && ph > 0 && pw > 0 && ph <= H && pw <= W, "patch apply + rect paste: bad shape");
+  UFR_REQUIRE((long)B * 3 * ph * pw < (1L << 30), "patch apply + rect paste: too many patch pixels");
+  const int n = 3 * ph * pw;
+  hipLaunchKernelGGL(patch_apply_paste_rect_kernel, dim3(ufr::ceil_div(n + 1, 256)), dim3(256), 0, ufr::as_stream(stream), rows,
+                     n_rows, patch_p, loss, tgt, ref, mask_p, origins, adv_tgt, adv_ref, B, H, W, ph, pw, step, bound, do_clamp, lo,
+                     hi, gate_state);
+  return ufr::launched("patch_apply_paste_rect_kernel");
 }
 
 extern "C" int ufr_normalize_frames(const float* frames_a, const float* frames_b, float* out, int Ba, int Bb, int C, int H, int W,

@@ -379,8 +379,97 @@ __global__ __launch_bounds__(256) void window_scatter_planes_kernel(const float*
   }
 }
 
+// The windowed prefix's conv2 (first frames) and conv3 (both frames) from their window planes into the head's buffers in one launch:
+// what chunks_to_nchw x2 + window_scatter_planes x3 + window_scatter do.  A thread takes 8 channels of one window cell: v = (p0 + p1)
+// + p2 (the float32 the NCHW form holds), planes = split3(v).  conv3's v also goes to the window's own NCHW tensor (every cell: the
+// backward reads LeakyReLU's sign from it) and, like the planes, to the full-frame NCHW conv3 outside the inexact rim.
+struct WinFeatArgs {
+  const __bf16 *c2w, *c3w;
+  long c2w_stride, c3w_stride, cat2_stride, c3a_stride, c3b_stride;
+  __bf16 *cat2, *c3a, *c3b;
+  float *c3_nchw, *c3w_nchw;
+  const int* win;
+  int B, h4, w4, h8, w8, wh4, ww4, wh8, ww8, m2, m3;
+  long total2, total;
+};
+
+__global__ __launch_bounds__(256) void window_features_kernel(const WinFeatArgs a) {
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < a.total; t += (long)gridDim.x * blockDim.x) {
+    const bool is3 = t >= a.total2;
+    long r = is3 ? t - a.total2 : t;
+    const int wh = is3 ? a.wh8 : a.wh4, ww = is3 ? a.ww8 : a.ww4, Hd = is3 ? a.h8 : a.h4, Wd = is3 ? a.w8 : a.w4;
+    const int groups = is3 ? 32 : 16, ls = is3 ? 8 : 4, margin = is3 ? a.m3 : a.m2;
+    const int j = (int)(r % ww); r /= ww;
+    const int i = (int)(r % wh); r /= wh;
+    const int g8 = (int)(r % groups);
+    const int n = (int)(r / groups);
+    const int* w = a.win + (n % a.B) * 8;
+    const int y0 = min(max(w[0] / ls, 0), Hd - wh), x0 = min(max(w[1] / ls, 0), Wd - ww);
+    const bool rim = (i < margin && y0 > 0) || (i >= wh - margin && y0 + wh < Hd) || (j < margin && x0 > 0) ||
+                     (j >= ww - margin && x0 + ww < Wd);
+    if (rim && !is3) continue;
+    const long Msrc = 2L * a.B * wh * ww;          // the window planes hold both frames' images at either level
+    const __bf16* s = (is3 ? a.c3w : a.c2w) + (((long)(g8 >> 2) * Msrc) + ((long)n * wh + i) * ww + j) * 32 + (g8 & 3) * 8;
+    const long ss = is3 ? a.c3w_stride : a.c2w_stride;
+    const bf16x8 p0 = *reinterpret_cast<const bf16x8*>(s), p1 = *reinterpret_cast<const bf16x8*>(s + ss),
+                 p2 = *reinterpret_cast<const bf16x8*>(s + 2 * ss);
+    float v[8];
+    bf16x8 q0, q1, q2;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      v[k] = ((float)p0[k] + (float)p1[k]) + (float)p2[k];
+      __bf16 x, y, z;
+      split3(v[k], x, y, z);
+      q0[k] = x; q1[k] = y; q2[k] = z;
+    }
+    if (is3) {
+      float* wo = a.c3w_nchw + (((long)n * 256 + g8 * 8) * wh + i) * ww + j;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) wo[(long)k * wh * ww] = v[k];
+      if (rim) continue;
+      float* fo = a.c3_nchw + (((long)n * 256 + g8 * 8) * Hd + y0 + i) * Wd + x0 + j;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) fo[(long)k * Hd * Wd] = v[k];
+    }
+    const int nd = (is3 && n >= a.B) ? n - a.B : n;
+    __bf16* d = is3 ? (n >= a.B ? a.c3b : a.c3a) : a.cat2;
+    const long ds = is3 ? (n >= a.B ? a.c3b_stride : a.c3a_stride) : a.cat2_stride;
+    const long Mdst = (long)a.B * Hd * Wd;
+    __bf16* o = d + (((long)(g8 >> 2) * Mdst) + ((long)nd * Hd + y0 + i) * Wd + x0 + j) * 32 + (g8 & 3) * 8;
+    *reinterpret_cast<bf16x8*>(o) = q0;
+    *reinterpret_cast<bf16x8*>(o + ds) = q1;
+    *reinterpret_cast<bf16x8*>(o + 2 * ds) = q2;
+  }
+}
 
 }  // namespace
+
+extern "C" int ufr_window_features_planes(const void* c2w, long c2w_stride, const void* c3w, long c3w_stride, void* cat2,
+                                          long cat2_stride, void* c3a, long c3a_stride, void* c3b, long c3b_stride, float* c3_nchw,
+                                          float* c3w_nchw, const int* win, int B, int H, int W, int wh, int ww, int m2, int m3,
+                                          ufr_stream_t stream) {
+  UFR_REQUIRE(c2w && c3w && cat2 && c3a && c3b && c3_nchw && c3w_nchw && win, "window features: null pointer");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && wh > 0 && ww > 0 && H % 8 == 0 && W % 8 == 0 && wh % 8 == 0 && ww % 8 == 0 && wh <= H &&
+                  ww <= W, "window features: bad shape (frame %dx%d, window %dx%d)", H, W, wh, ww);
+  UFR_REQUIRE(m2 >= 0 && m3 >= 0 && 2 * m2 <= wh / 4 && 2 * m2 <= ww / 4 && 2 * m3 <= wh / 8 && 2 * m3 <= ww / 8,
+              "window features: bad margins");
+  WinFeatArgs a;
+  a.c2w = static_cast<const __bf16*>(c2w); a.c3w = static_cast<const __bf16*>(c3w);
+  a.c2w_stride = c2w_stride; a.c3w_stride = c3w_stride; a.cat2_stride = cat2_stride; a.c3a_stride = c3a_stride; a.c3b_stride = c3b_stride;
+  a.cat2 = static_cast<__bf16*>(cat2); a.c3a = static_cast<__bf16*>(c3a); a.c3b = static_cast<__bf16*>(c3b);
+  a.c3_nchw = c3_nchw; a.c3w_nchw = c3w_nchw; a.win = win;
+  a.B = B; a.h4 = H / 4; a.w4 = W / 4; a.h8 = H / 8; a.w8 = W / 8;
+  a.wh4 = wh / 4; a.ww4 = ww / 4; a.wh8 = wh / 8; a.ww8 = ww / 8; a.m2 = m2; a.m3 = m3;
+  // every plane holds the chunks that are walked: 4 / 8 chunks of the window's 2B images, of the frame's B images
+  UFR_REQUIRE(c2w_stride >= 4L * 2 * B * a.wh4 * a.ww4 * 32 && c3w_stride >= 8L * 2 * B * a.wh8 * a.ww8 * 32,
+              "window features: the window planes do not hold 2 x %d images", B);
+  UFR_REQUIRE(cat2_stride >= 4L * B * a.h4 * a.w4 * 32 && c3a_stride >= 8L * B * a.h8 * a.w8 * 32 &&
+                  c3b_stride >= 8L * B * a.h8 * a.w8 * 32, "window features: the frame planes do not hold %d images", B);
+  a.total2 = (long)B * 16 * a.wh4 * a.ww4;
+  a.total = a.total2 + 2L * B * 32 * a.wh8 * a.ww8;
+  window_features_kernel<<<ufr::stream_grid(a.total, 256), 256, 0, ufr::as_stream(stream)>>>(a);
+  return ufr::launched("window_features_kernel");
+}
 
 extern "C" int ufr_window_scatter_planes(const float* src, void* planes, long plane_stride, int chunk0, const int* win,
                                          int n_win, int N, int C, int Hd, int Wd, int wh, int ww, int level_stride, int margin,

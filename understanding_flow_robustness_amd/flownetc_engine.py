@@ -429,18 +429,24 @@ class FlowNetCHeadEngine:
         self._wprefix = P
         return P
 
-    def window_prefix_forward(self, xw: torch.Tensor, win: torch.Tensor, m2: int, m3: int):
+    def window_prefix_forward(self, xw: torch.Tensor, win: torch.Tensor, m2: int, m3: int, c2_nchw: bool = True):
         """conv1-3 of the window stack `xw` [2B, 3, wh, ww] (raw frames; first frames, then second frames), patched into the
         cached full-frame features.  The window's convolutions zero-pad at the window's edges exactly like the torch
-        prefix they replace; the inexact rim (m2 / m3 cells) is skipped by the scatter."""
+        prefix they replace; the inexact rim (m2 / m3 cells) is skipped by the scatter.  `c2_nchw=False` leaves P["c2_nchw"]
+        (the window's conv2 as NCHW float32, which nothing on the attack's path reads) unwritten."""
         wh, ww = int(xw.shape[2]), int(xw.shape[3])
         P = self.window_prefix(wh, ww)
         self._conv1(P, xw.detach(), None)
         for _, launch, _ in P["fwd"]:
             launch()
-        P["c2"].to_nchw(128, 0, out=P["c2_nchw"])                         # (the scatter kernels take NCHW windows)
-        P["c3"].to_nchw(256, 0, out=P["c3_nchw"])
-        self.scatter_window_features(P["c2_nchw"], P["c3_nchw"], win, wh, ww, m2, m3)
+        # planes -> planes, + conv3 as float32 for the correlation and (P["c3_nchw"], every cell) for the backward's LeakyReLU'
+        c2, c3, H, W = P["c2"], P["c3"], self.H, self.W
+        L.check(L.lib().ufr_window_features_planes(
+            L.ptr(c2.t), c2.plane_stride, L.ptr(c3.t), c3.plane_stride, L.ptr(self.cat2.t), self.cat2.plane_stride,
+            L.ptr(self.c3a_p.t), self.c3a_p.plane_stride, L.ptr(self.c3b_p.t), self.c3b_p.plane_stride, L.ptr(self.c3_nchw),
+            L.ptr(P["c3_nchw"]), L.ptr(win), self.B, H, W, wh, ww, int(m2), int(m3), L.stream()), "window features -> planes")
+        if c2_nchw:
+            c2.to_nchw(128, 0, out=P["c2_nchw"])
 
     def window_gather_conv2_gradient(self, win: torch.Tensor, m2: int):
         """The conv2 tap's window gradient straight from the head's chunk-major sum of cat2 (chunks 0-3 = conv2 of the
@@ -451,10 +457,11 @@ class FlowNetCHeadEngine:
         L.check(L.lib().ufr_window_gather_chunks(L.ptr(self.G_cat2.t), L.ptr(P["G_gw2"].t), L.ptr(win), self.B, self.B, 2 * self.B, 4,
                                                  h4, w4, wh // 4, ww // 4, 4, int(m2), L.stream()), "window gather (chunks)")
 
-    def window_prefix_backward(self, gw3: torch.Tensor, gw2: torch.Tensor | None = None) -> torch.Tensor:
+    def window_prefix_backward(self, gw3: torch.Tensor, gw2: torch.Tensor | None = None, unpack: bool = True) -> torch.Tensor:
         """d loss / d xw from the window gradients of the two taps: gw3 [2B, 256, wh/8, ww/8] (conv3 of both frames, rim
         zeroed); the conv2 tap's (first frames) was put into `G_gw2` by `window_gather_conv2_gradient`, or is handed over
-        here as NCHW [B, 128, wh/4, ww/4]."""
+        here as NCHW [B, 128, wh/4, ww/4].  `unpack=False` returns conv1's packed gradient sum [1, 2B (wh/2+3) (ww/2+2), 32]
+        instead (ufr_patch_grad_crop_packed reads it through the unpacking's index map)."""
         P, B = self._wprefix, self.B
         wh, ww = P["hw"]
         if gw2 is not None:                      # NCHW -> chunk-major addend (tests, callers without the engine's sums)
@@ -468,6 +475,8 @@ class FlowNetCHeadEngine:
         # tap's output is reached; conv1's -> gradient of the packed planes -> gradient of the raw window stack
         for _, launch, _ in P["bwd"]:
             launch()
+        if not unpack:
+            return P["G_p"].t
         L.check(L.lib().ufr_conv1_unpack_grad(L.ptr(P["G_p"].t), L.ptr(P["gxw"]), 2 * B, wh, ww, L.stream()), "conv1 unpack")
         return P["gxw"]
 

@@ -112,7 +112,9 @@ class PatchAttackStep:
         pb = 1 if shared_patch else batch
         self.tgt = torch.zeros(batch, 3, height, width, **f32)
         self.ref = torch.zeros_like(self.tgt)
-        self.mask = torch.zeros_like(self.tgt)            # canvas masks (placed mode: written by the placed paste)
+        # canvas masks; a patch-coordinate step fills them when `mask` is first read after a load()
+        self._mask_canvas = None if self.placed else torch.zeros_like(self.tgt)
+        self._mask_stale = self.placed
         if self.placed:
             ph, pw = (int(v) for v in patch_hw)
             if not (0 < ph <= height and 0 < pw <= width):
@@ -160,6 +162,19 @@ class PatchAttackStep:
         self.win = torch.zeros(batch, 8, dtype=torch.int32, device=self.dev)     # one window per pair
         self.patch_loaded = torch.zeros_like(self.patch) if self.cone is not None else None
 
+    @property
+    def mask(self):
+        """The canvas masks [B,3,H,W].  In patch coordinates nothing on the attack path reads them: load() leaves them stale and
+        the first read places `mask_p` at the loaded origins."""
+        if self.placed and self._mask_stale:
+            if self._mask_canvas is None:
+                self._mask_canvas = torch.zeros_like(self.tgt)
+            with torch.cuda.device(self.dev):
+                L.check(L.lib().ufr_patch_mask_placed(L.ptr(self.mask_p), L.ptr(self.origins), L.ptr(self._mask_canvas), self.B,
+                                                      self.H, self.W, self.ph, self.pw, L.stream()), "placed mask")
+            self._mask_stale = False
+        return self._mask_canvas
+
     # ------------------------------------------------------------------------------------ C ABI calls
     def _paste(self, do_clamp, gate=False, write_mask=False):
         if self.placed and self._rect_paste and not write_mask:
@@ -171,9 +186,8 @@ class PatchAttackStep:
             return
         if self.placed:
             L.check(L.lib().ufr_patch_paste_placed(
-                L.ptr(self.tgt), L.ptr(self.ref), L.ptr(self.patch), L.ptr(self.mask_p), L.ptr(self.origins),
-                self.origins_host.ctypes.data if (write_mask and self.origins_host is not None) else None,
-                L.ptr(self.adv_tgt), L.ptr(self.adv_ref), L.ptr(self.mask) if write_mask else None, self.B, self.H,
+                L.ptr(self.tgt), L.ptr(self.ref), L.ptr(self.patch), L.ptr(self.mask_p), L.ptr(self.origins), None,
+                L.ptr(self.adv_tgt), L.ptr(self.adv_ref), None, self.B, self.H,
                 self.W, self.ph, self.pw, int(do_clamp), self.lo, self.hi, L.ptr(self.state) if gate else None,
                 L.stream()), "placed paste")
             return
@@ -199,10 +213,19 @@ class PatchAttackStep:
     def _apply(self):
         """Patch-coordinate form, common half (after the all-gather): fixed-order sum of every rank's rows, the
         clamped step on P, re-paste of every pair (main.py:581-600)."""
+        if self._rect_paste:                   # later iterations: step and rectangle re-paste are one launch
+            return self._apply_rect()
         L.check(L.lib().ufr_patch_apply(L.ptr(self.rows_all), self.rows_all.shape[0], L.ptr(self.patch),
                                         L.ptr(self.loss_cur), self.ph, self.pw, self.step, CLAMP_BOUND,
                                         L.ptr(self.state), L.stream()), "patch apply")
         self._paste(do_clamp=True, gate=True)
+
+    def _apply_rect(self):
+        """`_apply` of the later iterations in one launch: the step on P and the re-paste of the patch rectangles."""
+        L.check(L.lib().ufr_patch_apply_paste_rect(
+            L.ptr(self.rows_all), self.rows_all.shape[0], L.ptr(self.patch), L.ptr(self.loss_cur), L.ptr(self.tgt), L.ptr(self.ref),
+            L.ptr(self.mask_p), L.ptr(self.origins), L.ptr(self.adv_tgt), L.ptr(self.adv_ref), self.B, self.H, self.W, self.ph,
+            self.pw, self.step, CLAMP_BOUND, 1, self.lo, self.hi, L.ptr(self.state), L.stream()), "patch apply + rect paste")
 
     # ------------------------------------------------------------------------------------ windowed encoder
     def _mask_extent(self):
@@ -297,6 +320,10 @@ class PatchAttackStep:
             if self.band.corr_width:
                 from .band_conv import corr_band_origin
                 self.band.win[:, 2] = corr_band_origin(self.win[:, 1], self.band.corr_width, self.W)
+        self._cone_prefix(prefix_features)
+
+    def _cone_prefix(self, prefix_features=None):
+        """The full-frame prefix of a call (`_cone_refresh`), once the window and band origins are on the device."""
         if self.eng is not None:
             if prefix_features is not None:
                 self.eng.load_prefix_features(*prefix_features)
@@ -313,8 +340,9 @@ class PatchAttackStep:
     def _forward_cone(self):
         """Prefix on the window, paste into the cached full features, head at full size."""
         lib, B, H, W = L.lib(), self.B, self.H, self.W
-        self._win_copy(lib.ufr_window_gather, self.adv_tgt, self.xw, B, 3, H, W, 1, 0)
-        self._win_copy(lib.ufr_window_gather, self.adv_ref, self.xw[B:], B, 3, H, W, 1, 0)
+        wh, ww = self.win_hw               # both stacks' windows in one launch, which also zeroes the loss accumulator (`_part_a`)
+        L.check(lib.ufr_window_gather_pair(L.ptr(self.adv_tgt), L.ptr(self.adv_ref), L.ptr(self.xw), L.ptr(self.win),
+                                           L.ptr(self.loss_local), B, 3, H, W, wh, ww, L.stream()), "window gather (pair)")
         if self.eng is not None:               # the window's prefix on the engine too (no autograd graph)
             self._feats_w = None
             if self.eng_kind == "pwc":
@@ -322,7 +350,7 @@ class PatchAttackStep:
                 self.eng.forward_cached()
             else:
                 (_, m2, _, _, _), (_, m3, _, _, _) = self.taps
-                self.eng.window_prefix_forward(self.xw, self.win, m2, m3)
+                self.eng.window_prefix_forward(self.xw, self.win, m2, m3, c2_nchw=False)
                 self.eng.forward_cached(self.band)
             if self._fused_loss:                   # the loss kernel upsamples flow2 itself (no full-size flow)
                 return None
@@ -339,6 +367,7 @@ class PatchAttackStep:
         """Adjoint of the head at full size, of the prefix on the window; canvas-sized gradients that are
         zero outside the window (only mask * gradient is ever used, main.py:575-583)."""
         lib, B, H, W = L.lib(), self.B, self.H, self.W
+        self._packed_grad = False
         if self.eng is not None:
             if flow is None:                     # ufr_flow2_upsampled_loss wrote d loss / d flow2 itself
                 g_flow2 = self.g_flow2
@@ -360,7 +389,10 @@ class PatchAttackStep:
                 if g3a is not None:
                     self._win_copy(lib.ufr_window_gather, g3a, gw3, B, 256, H // ls3, W // ls3, ls3, m3)
                     self._win_copy(lib.ufr_window_gather, g3b, gw3[B:], B, 256, H // ls3, W // ls3, ls3, m3)
-                gxw = self.eng.window_prefix_backward(self.taps[1][4], None if g2a is None else self.taps[0][4])
+                # a patch-coordinate step crops straight from conv1's packed gradient sum: the window gradients are not unpacked
+                self._packed_grad = self.placed
+                gxw = self.eng.window_prefix_backward(self.taps[1][4], None if g2a is None else self.taps[0][4],
+                                                      unpack=not self.placed)
         else:
             g_full = torch.autograd.grad(flow, [t[3] for t in self.taps], self.g_flow)
             for g, (ls, m, n, _, gwin) in zip(g_full, self.taps):
@@ -378,10 +410,10 @@ class PatchAttackStep:
     def _part_a(self):
         """forward -> loss (+ d loss/d flow) -> data-gradient backward -> update (or, patch-coordinate form on
         several ranks: this rank's cropped gradient rows; the all-gather and `_part_b` follow)."""
-        self.loss_local.zero_()
         if self.cone is not None:
-            flow = self._forward_cone()
+            flow = self._forward_cone()            # (zeroes loss_local with its window gather)
         else:
+            self.loss_local.zero_()
             flow = predict_flow(self.net, None, self.adv_tgt, self.adv_ref, self.args)
         # shared patch: loss = mean over the GLOBAL batch; private: every sample its own mean
         weight = (1.0 - self.alpha) * ((1.0 / self.world) if self.shared else float(self.B))
@@ -412,9 +444,10 @@ class PatchAttackStep:
             self._update(g_tgt, g_ref)
             self._gate()
             return
-        if g_ref is None:                      # windowed prefix: crop from the window gradients [2B,3,wh,ww]
+        if g_ref is None:                      # windowed prefix: crop from the window gradients [2B,3,wh,ww] (or their packed sum)
             wh, ww = self.win_hw
-            L.check(L.lib().ufr_patch_grad_crop_window(L.ptr(g_tgt), L.ptr(self.win), L.ptr(self.mask_p), L.ptr(self.origins),
+            crop = L.lib().ufr_patch_grad_crop_packed if self._packed_grad else L.lib().ufr_patch_grad_crop_window
+            L.check(crop(L.ptr(g_tgt), L.ptr(self.win), L.ptr(self.mask_p), L.ptr(self.origins),
                                                        L.ptr(self.loss_local), L.ptr(self.rows_local), self.B, self.H, self.W, wh, ww,
                                                        self.ph, self.pw, self.groups, L.stream()), "patch grad crop (window)")
         else:
@@ -504,26 +537,12 @@ class PatchAttackStep:
         Patch-coordinate steps (`patch_hw`): patch / mask / patch_init are [1,3,ph,pw], `origins` [B,2] holds each
         pair's (row, column); canvas steps: canvas-sized tensors like the reference's.
         `prefix_features`: see `_cone_refresh` (ignored by the full-frame iteration)."""
+        if self.placed:
+            return self._load_placed(tgt, ref, patch, mask, patch_init, target, prefix_features, origins)
         with torch.no_grad():
             self.tgt.copy_(tgt); self.ref.copy_(ref)
-            if self.placed:
-                if origins is None:
-                    raise ValueError("a patch-coordinate step needs origins=[B,2] (row, column of every pair's patch)")
-                if torch.is_tensor(origins):
-                    self.origins.copy_(origins.reshape(self.B, 2))
-                    self.origins_host = None              # device-resident placements: not validated on the host
-                else:
-                    oh = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(self.B, 2))
-                    if (oh < 0).any() or (oh[:, 0] + self.ph > self.H).any() or (oh[:, 1] + self.pw > self.W).any():
-                        raise ValueError("a patch placement leaves the frame")
-                    self.origins_host = oh
-                    self.origins.copy_(torch.from_numpy(oh))
-                self.mask_p.copy_(mask.reshape(self.mask_p.shape))
-                self.patch.copy_(patch.reshape(self.patch.shape))
-                self.patch_init.copy_(patch_init.reshape(self.patch.shape))
-            else:
-                self.mask.copy_(mask.expand_as(self.mask))
-                self.patch.copy_(patch); self.patch_init.copy_(patch_init)
+            self.mask.copy_(mask.expand_as(self.mask))
+            self.patch.copy_(patch); self.patch_init.copy_(patch_init)
             self.target.copy_(target)
             self.state.zero_()
             self._paste(do_clamp=False, write_mask=True)
@@ -534,6 +553,63 @@ class PatchAttackStep:
                     self._setup_cone()
                 if self.cone is not None:
                     self._cone_refresh(prefix_features)
+
+    def _operand(self, t, like):
+        """A caller's tensor as the native load kernels read it: float32, contiguous, on the step's device, `like`'s shape (no copy
+        when it already is)."""
+        t = t.detach().to(device=self.dev, dtype=torch.float32)
+        if t.shape != like.shape:
+            t = t.expand_as(like) if t.dim() == like.dim() else t.reshape(like.shape)
+        return t.contiguous()
+
+    def _place(self, patch, mask, patch_init, origins_dev, with_cone):
+        """One launch (csrc/window.hip): patch-coordinate operands and origins into the static buffers, state = 0 and, with a sized
+        window, the window table, the overflow flag and the band origins (what ufr_cone_window and the torch band arithmetic of
+        `_cone_refresh` compute from the canvas masks)."""
+        band = self.band if with_cone else None
+        banded = band is not None and band.width
+        wh, ww = self.win_hw if with_cone else (0, 0)
+        from .band_conv import CORR_REACH
+        L.check(L.lib().ufr_attack_place(
+            L.ptr(patch), L.ptr(mask), L.ptr(patch_init), L.ptr(origins_dev) if origins_dev is not None else None,
+            self.origins_host.ctypes.data if origins_dev is None else None, L.ptr(self.patch), L.ptr(self.mask_p),
+            L.ptr(self.patch_init), L.ptr(self.patch_loaded) if self.patch_loaded is not None else None, L.ptr(self.origins),
+            L.ptr(self.state), self.B, self.H, self.W, self.ph, self.pw, C.byref(self._chain) if with_cone else None, wh, ww,
+            L.ptr(self.win), L.ptr(band.win) if banded else None, band.width if banded else 0,
+            self._band_reach if banded else 0, band.corr_width if banded else 0, CORR_REACH, L.stream()), "attack place")
+
+    def _load_placed(self, tgt, ref, patch, mask, patch_init, target, prefix_features, origins):
+        """load() of a patch-coordinate step: a placement launch, a frame launch that reads the caller's frames once (the step's
+        copies and the first, un-clamped paste), the target copy, the full-frame prefix.  The canvas masks are not written
+        (`mask`)."""
+        if origins is None:
+            raise ValueError("a patch-coordinate step needs origins=[B,2] (row, column of every pair's patch)")
+        origins_dev = None
+        if torch.is_tensor(origins):
+            origins_dev = origins.detach().to(device=self.dev, dtype=torch.int32).reshape(self.B, 2).contiguous()
+            self.origins_host = None              # device-resident placements: not validated on the host
+        else:
+            oh = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(self.B, 2))
+            if (oh < 0).any() or (oh[:, 0] + self.ph > self.H).any() or (oh[:, 1] + self.pw > self.W).any():
+                raise ValueError("a patch placement leaves the frame")
+            self.origins_host = oh
+        with torch.no_grad(), torch.cuda.device(self.dev):
+            tgt, ref = self._operand(tgt, self.tgt), self._operand(ref, self.tgt)
+            ops = [self._operand(t, self.patch) for t in (patch, mask, patch_init)]
+            sized = self.cone is not None and self.win_hw is not None
+            self._place(*ops, origins_dev, with_cone=sized)
+            L.check(L.lib().ufr_attack_load_frames(
+                L.ptr(tgt), L.ptr(ref), L.ptr(self.patch), L.ptr(self.mask_p), L.ptr(self.origins), L.ptr(self.tgt), L.ptr(self.ref),
+                L.ptr(self.adv_tgt), L.ptr(self.adv_ref), self.B, self.H, self.W, self.ph, self.pw, L.stream()), "attack load frames")
+            self.target.copy_(target)
+            self._mask_stale = True
+            self._first = True                 # the next iteration sees new frames: full head forward
+            if self.cone is not None and not sized:
+                self._setup_cone()             # first load: the window is sized from the masks (host read), then placed
+                if self.cone is not None:
+                    self._place(self.patch, self.mask_p, self.patch_init, self.origins, with_cone=True)
+            if self.cone is not None:
+                self._cone_prefix(prefix_features)
 
     def run(self, max_count):
         """Enqueue up to `max_count` iterations back to back; returns (executed, last_loss) after ONE

@@ -957,6 +957,43 @@ int ufr_grad_norm(const ufr_adamw_seg* segs, int nseg, float max_norm, double* p
                   ufr_stream_t stream);
 int ufr_adamw_step(const ufr_adamw_seg* segs, int nseg, const ufr_adamw_hyper* h, const float* norm, ufr_stream_t stream);
 
+/* ---- patch location sweep (csrc/patch_sweep.hip) -----------------------------------------------------------------------------
+ * patch_attacks/test_moving_patch.py:299-445 moves the finished patch over ONE clean frame pair and records the end-point error
+ * and the cosine similarity at every position.  K positions of a chunk are served by two entries; origins[k] = (row, column),
+ * int32 on the device as for ufr_patch_paste_placed, and `origins_host`, the same table on the host, is REQUIRED: every origin
+ * is checked against [0, H - ph] x [0, W - pw] before any launch (the kernels index the frame without clipping).
+ *
+ * ufr_sweep_paste: tgt / ref [3,H,W] -> K adversarial pairs, the arithmetic and rounding order of ufr_patch_paste_placed with
+ *   do_clamp = 1 (adv = clamp((1 - M_k) * img + M_k * place(patch_p), lo, hi)).
+ *   canvas form (win == NULL): adv_tgt / adv_ref [K,3,H,W] in one launch.
+ *   window form (win != NULL; needs chain and xw): a one-workgroup launch writes win[k], the table ufr_cone_window computes from the
+ *     canvas masks (their box is origin + the box of mask_p != 0), then one launch writes xw [2K,3,win_h,win_w] = the windows of
+ *     the K pasted first frames, then of the K pasted second frames: what ufr_patch_paste_placed + ufr_window_gather_pair write, bit
+ *     for bit, without the canvases.  adv_tgt / adv_ref are not read.
+ *   16-byte accesses when the rows allow it (W, win_w and the chain's total stride multiples of 4, pointers 16-byte aligned).
+ * ufr_sweep_metrics: pred [K,2,H,W] (the network's flow at frame size), gt [3,Hg,Wg] = (u, v, valid) -> out[row0 + k] =
+ *   (adv_epe_k, adv_cos_sim_k), float32 pairs of a result buffer of `rows` rows.  For every ground-truth pixel, in one pass:
+ *     p  = pred_k resized bilinearly to Hg x Wg, align_corners = False (source (dst + 0.5) * in / out - 0.5 clamped at 0, the
+ *          neighbour index clamped to the last row / column: the identity when the sizes agree);
+ *     m  = the canvas mask M_k (mask_p at origins[k], 0 elsewhere) resized the same way, channel for channel;
+ *     g  = (1 - m) * gt + m * (0, 0, valid_in_patch)                                  (test_moving_patch.py:353-362, :413-432)
+ *     epe = |(g_u - p_u * Wg/W, g_v - p_v * Hg/H)|,  cos = sum_c (g_c / max(|g|, 1e-8)) * (p_c / max(|p|, 1e-8))
+ *          (patch_attacks/losses.py:8-50, torch.nn.functional.cosine_similarity), both weighted by g_valid;
+ *   out = sum(valid * epe) / (sum(valid) + 1e-8), sum(valid * cos) / (sum(valid) + 1e-8).  mask_p == NULL: no patch (m = 0, the
+ *   clean metrics; origins are not read).  All per-pixel arithmetic and the three sums are float64; workgroup partials in `ws`
+ *   (ufr_sweep_metrics_workspace_doubles(K) doubles) are added in a fixed order by a second launch: no float atomics, two runs
+ *   are bit-identical.  Neither the canvas mask nor g nor the resized prediction is written to memory.
+ * Refused (UFR_EINVAL + ufr_last_error) before any launch: null pointers, K < 1, non-positive sizes, a patch larger than the frame,
+ * an origin outside the frame, lo > hi, a window form without a chain or xw, a bad chain or window size, valid_in_patch other than
+ * 0 / 1, rows outside the result buffer, a workspace that is too small. */
+int ufr_sweep_paste(const float* tgt, const float* ref, const float* patch_p, const float* mask_p, const int* origins,
+                    const int* origins_host, float* adv_tgt, float* adv_ref, int K, int H, int W, int ph, int pw, float lo, float hi,
+                    const ufr_cone_chain* chain, int win_h, int win_w, int* win, float* xw, ufr_stream_t stream);
+long ufr_sweep_metrics_workspace_doubles(int K);   /* -1 when K < 1 */
+int ufr_sweep_metrics(const float* pred, const float* gt, const float* mask_p, const int* origins, const int* origins_host, int K,
+                      int H, int W, int Hg, int Wg, int ph, int pw, int valid_in_patch, double* ws, long ws_elems, float* out,
+                      int row0, int rows, ufr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

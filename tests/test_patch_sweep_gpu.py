@@ -1,0 +1,298 @@
+"""GPU suite of the patch location sweep (patch_sweep.py, csrc/patch_sweep.hip): the paste entry against the entries it fuses (bit for
+bit), the metrics entry against a float64 restatement, the windowed path against the generic one, the generic path against the
+reference's literal loop (test_moving_patch.py:299-445 restated with this project's mirrors at batch 1), a second network, and
+the state the sweep leaves behind on the engine it shares with the attack steps."""
+import ctypes as C
+from argparse import Namespace
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+F32 = dict(dtype=torch.float32, device=DEV)
+H, W, S, STRIDE = 128, 256, 19, 32
+
+
+def _L():
+    from understanding_flow_robustness_amd import _lib as L
+    return L
+
+
+def _disc(side):
+    from understanding_flow_robustness_amd.utils_patch import createCircularMask
+    d = createCircularMask(side, side).astype("float32")
+    return np.array([[d, d, d]])
+
+
+@pytest.fixture(scope="module")
+def net():
+    from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
+    return fetch_model(Namespace(flownet="FlowNetC"), synthetic_seed=0).to(DEV)
+
+
+ARGS = Namespace(flownet="FlowNetC", norotate=True, l2=False, alpha=0.0, lr=1.0e3, max_count=2)
+
+
+@pytest.fixture(scope="module")
+def scene():
+    """One frame pair, a ground truth of another size whose valid channel has zeros, a patch that leaves [0, 1]."""
+    g = torch.Generator().manual_seed(41)
+    tgt, ref = torch.rand(1, 3, H, W, generator=g).to(DEV), torch.rand(1, 3, H, W, generator=g).to(DEV)
+    uv = torch.randn(1, 2, 120, 250, generator=g) * 5.0
+    valid = (torch.rand(1, 1, 120, 250, generator=g) > 0.3).float()
+    gt = torch.cat((uv, valid), 1).to(DEV)
+    patch = np.random.RandomState(5).rand(1, 3, S, S) * 1.2 - 0.1
+    return tgt, ref, gt, patch, _disc(S)
+
+
+def _sweep(net, scene, args=ARGS, stride=STRIDE, **kw):
+    """(result, flows of every position [n,2,H,W]) through the function's private debug hook."""
+    from understanding_flow_robustness_amd.patch_sweep import sweep_patch_locations
+    got = []
+    sweep_patch_locations._debug_flows = lambda row0, flow: got.append(flow.detach().clone())
+    try:
+        res = sweep_patch_locations(net, *scene, args, stride=stride, **kw)
+    finally:
+        sweep_patch_locations._debug_flows = None
+    return res, torch.cat(got)[:len(res.locations)]
+
+
+@pytest.fixture(scope="module")
+def generic(net, scene):
+    return _sweep(net, scene, chunk=5, cone=False)
+
+
+def _literal_loop(flow_net, args, tgt, ref, gt, patch, mask, stride):
+    """test_moving_patch.py:280-445 (whole_img == 0, circle, norotate, no calibration), line for line at batch 1."""
+    from understanding_flow_robustness_amd.flownets.utils_model import predict_flow
+    from understanding_flow_robustness_amd.losses import compute_cossim, compute_epe
+    from understanding_flow_robustness_amd.utils_patch import circle_transform
+    with torch.no_grad():
+        flow_fwd = predict_flow(flow_net, None, tgt, ref, args)
+    epe, cos_sim = compute_epe(gt=gt, pred=flow_fwd), compute_cossim(gt, flow_fwd)
+    data_shape, patch_shape = tuple(tgt.shape), patch.shape
+    ny, nx = len(range(0, data_shape[-2] - patch_shape[-2], stride)), len(range(0, data_shape[-1] - patch_shape[-1], stride))
+    adv_image, cos_image, worst, worst_epe = np.zeros((ny, nx)), np.zeros((ny, nx)), None, -1
+    bt, _, h_gt, w_gt = gt.shape
+    patch_flow = torch.cat((torch.zeros((bt, 2, h_gt, w_gt)), torch.ones((bt, 1, h_gt, w_gt))), 1).to(DEV)
+    for x in range(0, data_shape[-1] - patch_shape[-1], stride):
+        for y in range(0, data_shape[-2] - patch_shape[-2], stride):
+            patch_full, mask_full, _, _, _, _ = circle_transform(patch, mask, patch.copy(), data_shape, patch_shape, 0, norotate=True,
+                                                                 fixed_loc=(x, y), moving=True)
+            patch_var, mask_var = torch.FloatTensor(patch_full).to(DEV), torch.FloatTensor(mask_full).to(DEV)
+            adv_tgt = torch.clamp(torch.mul((1 - mask_var), tgt) + torch.mul(mask_var, patch_var), 0, 1)
+            adv_ref = torch.clamp(torch.mul((1 - mask_var), ref) + torch.mul(mask_var, patch_var), 0, 1)
+            with torch.no_grad():
+                adv_flow = predict_flow(flow_net, None, adv_tgt, adv_ref, args)
+            mask_res = F.interpolate(mask_var, size=(h_gt, w_gt), mode="bilinear", align_corners=False)
+            gt_adv = torch.mul((1 - mask_res), gt) + torch.mul(mask_res, patch_flow)
+            adv_epe = compute_epe(gt=gt_adv, pred=adv_flow)
+            adv_image[y // stride, x // stride] = adv_epe
+            cos_image[y // stride, x // stride] = compute_cossim(gt_adv, adv_flow)
+            if adv_epe > worst_epe:
+                worst_epe, worst = adv_epe, (y, x)
+    return adv_image, cos_image, epe, cos_sim, worst
+
+
+def _assert_maps(got, want_epe, want_cos, what):
+    e = np.abs(got.adv_epe - want_epe) / np.abs(want_epe)
+    c = np.abs(got.adv_cos_sim - want_cos)
+    print(f"{what}: EPE maps differ by {e.max():.2e} relative, cos-sim maps by {c.max():.2e} absolute")
+    assert e.max() <= 1e-4, f"{what}: EPE maps differ by {e.max():.2e} relative"
+    assert c.max() <= 1e-4, f"{what}: cos-sim maps differ by {c.max():.2e} absolute"
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1. paste
+def test_paste_equals_placed_paste_and_window_gather_bit_for_bit(net):
+    L = _L()
+    lib, st = L.lib(), L.stream()
+    K = 5
+    rows = [(0, 0), (109, 237), (0, 237), (50, 100), (109, 0)]
+    g = torch.Generator().manual_seed(7)
+    tgt = (torch.rand(1, 3, H, W, generator=g) * 1.2 - 0.1).to(DEV)          # values on both sides of the clamp
+    ref = (torch.rand(1, 3, H, W, generator=g) * 1.2 - 0.1).to(DEV)
+    patch_p = (torch.rand(1, 3, S, S, generator=g) * 1.4 - 0.2).to(DEV)
+    mask_p = torch.from_numpy(_disc(S)).to(DEV)
+    host = np.ascontiguousarray(np.asarray(rows, dtype=np.int32))
+    origins = torch.from_numpy(host).to(DEV)
+    spec = net.CONE
+    wh, ww = spec.window_size(S, H), spec.window_size(S, W)
+    chain = spec.to_c()
+    # the entries the sweep's paste fuses: placed paste of the frames repeated K times (+ canvas masks), window table, gather
+    tgt_K, ref_K = tgt.expand(K, -1, -1, -1).contiguous(), ref.expand(K, -1, -1, -1).contiguous()
+    adv_t, adv_r, masks = torch.zeros_like(tgt_K), torch.zeros_like(tgt_K), torch.zeros_like(tgt_K)
+    L.check(lib.ufr_patch_paste_placed(L.ptr(tgt_K), L.ptr(ref_K), L.ptr(patch_p), L.ptr(mask_p), L.ptr(origins), None, L.ptr(adv_t),
+                                       L.ptr(adv_r), L.ptr(masks), K, H, W, S, S, 1, 0.0, 1.0, None, st), "placed paste")
+    win_ref = torch.zeros(K, 8, dtype=torch.int32, device=DEV)
+    overflow = torch.zeros(1, **F32)
+    L.check(lib.ufr_cone_window(L.ptr(masks), K, 3 * H * W, 3, H, W, C.byref(chain), wh, ww, L.ptr(win_ref), L.ptr(overflow), st),
+            "cone window")
+    xw_ref = torch.zeros(2 * K, 3, wh, ww, **F32)
+    L.check(lib.ufr_window_gather_pair(L.ptr(adv_t), L.ptr(adv_r), L.ptr(xw_ref), L.ptr(win_ref), None, K, 3, H, W, wh, ww, st),
+            "gather pair")
+    assert float(overflow) == 0.0 and float((adv_t - tgt_K).abs().max()) > 0.1
+    # canvas form
+    got_t, got_r = torch.full_like(tgt_K, -7.0), torch.full_like(tgt_K, -7.0)
+    L.check(lib.ufr_sweep_paste(L.ptr(tgt), L.ptr(ref), L.ptr(patch_p), L.ptr(mask_p), L.ptr(origins), host.ctypes.data, L.ptr(got_t),
+                                L.ptr(got_r), K, H, W, S, S, 0.0, 1.0, None, 0, 0, None, None, st), "sweep paste")
+    assert torch.equal(got_t, adv_t) and torch.equal(got_r, adv_r)
+    # window form
+    win = torch.full((K, 8), -1, dtype=torch.int32, device=DEV)
+    xw = torch.full((2 * K, 3, wh, ww), -7.0, **F32)
+    L.check(lib.ufr_sweep_paste(L.ptr(tgt), L.ptr(ref), L.ptr(patch_p), L.ptr(mask_p), L.ptr(origins), host.ctypes.data, None, None, K,
+                                H, W, S, S, 0.0, 1.0, C.byref(chain), wh, ww, L.ptr(win), L.ptr(xw), st), "sweep paste (window)")
+    assert torch.equal(win, win_ref), (win.tolist(), win_ref.tolist())
+    assert torch.equal(xw, xw_ref)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 2. metrics
+def _restated_metrics(pred, gt, mask_p, rows, valid_in_patch, dtype):
+    """F.interpolate, the blend of test_moving_patch.py:413-432 and the formulas of losses.py in `dtype`, one position at a time."""
+    from understanding_flow_robustness_amd.losses import cossim_tensor, epe_tensor
+    out = []
+    gt1 = gt[None].to(dtype)
+    hg, wg = gt.shape[-2:]
+    for k in range(pred.shape[0]):
+        gt_adv = gt1
+        if mask_p is not None:
+            canvas = torch.zeros(1, 3, *pred.shape[-2:], dtype=dtype, device=DEV)
+            oy, ox = rows[k]
+            canvas[:, :, oy:oy + mask_p.shape[-2], ox:ox + mask_p.shape[-1]] = mask_p.to(dtype)
+            m = F.interpolate(canvas, size=(hg, wg), mode="bilinear", align_corners=False)
+            pf = torch.cat((torch.zeros(1, 2, hg, wg, dtype=dtype, device=DEV),
+                            torch.full((1, 1, hg, wg), float(valid_in_patch), dtype=dtype, device=DEV)), 1)
+            gt_adv = torch.mul((1 - m), gt1) + torch.mul(m, pf)
+        p = pred[k:k + 1].to(dtype)
+        out.append((float(epe_tensor(gt_adv, p)), float(cossim_tensor(gt_adv, p))))
+    return np.asarray(out, dtype=np.float64)
+
+
+def _run_metrics(pred, gt, mask_p, rows, valid_in_patch):
+    L = _L()
+    lib = L.lib()
+    K = pred.shape[0]
+    ws = torch.zeros(lib.ufr_sweep_metrics_workspace_doubles(K), dtype=torch.float64, device=DEV)
+    out = torch.full((K + 2, 2), -7.0, **F32)
+    host = np.ascontiguousarray(np.asarray(rows, dtype=np.int32))
+    origins = torch.from_numpy(host).to(DEV)
+    ph, pw = (mask_p.shape[-2], mask_p.shape[-1]) if mask_p is not None else (0, 0)
+    L.check(lib.ufr_sweep_metrics(L.ptr(pred), L.ptr(gt), L.ptr(mask_p) if mask_p is not None else None,
+                                  L.ptr(origins) if mask_p is not None else None, host.ctypes.data if mask_p is not None else None, K,
+                                  pred.shape[2], pred.shape[3], gt.shape[1], gt.shape[2], ph, pw, valid_in_patch, L.ptr(ws), ws.numel(),
+                                  L.ptr(out), 1, K + 2, L.stream()), "sweep metrics")
+    assert float(out[0].max()) == -7.0 and float(out[-1].max()) == -7.0        # only the caller's row range is written
+    return out[1:-1].clone()
+
+
+@pytest.mark.parametrize("hg,wg,valid_in_patch,with_mask", [(60, 100, 1, True), (60, 100, 0, True), (64, 96, 1, True),
+                                                           (60, 100, 1, False)])
+def test_metrics_against_float64_restatement(hg, wg, valid_in_patch, with_mask):
+    """Bound per value: the larger of 1e-6 * |value| (what tests/test_flow_oracle_cpu.py holds these metrics to) and 4 x the error
+    of the float32 torch spelling against the same float64 values (the kernel's per-pixel rounding sequence may differ from
+    torch's; its float64 sums are better than torch's float32 ones)."""
+    g = torch.Generator().manual_seed(100 * hg + valid_in_patch)
+    pred = (torch.randn(3, 2, 64, 96, generator=g) * 4.0).to(DEV)
+    gt = torch.cat((torch.randn(2, hg, wg, generator=g) * 4.0, (torch.rand(1, hg, wg, generator=g) > 0.25).float())).to(DEV)
+    rows = [(0, 0), (53, 85), (20, 40)]
+    mask_p = torch.from_numpy(_disc(11))[0].contiguous().to(DEV) if with_mask else None
+    want = _restated_metrics(pred, gt, mask_p, rows, valid_in_patch, torch.float64)
+    f32 = _restated_metrics(pred, gt, mask_p, rows, valid_in_patch, torch.float32)
+    out = _run_metrics(pred, gt, mask_p, rows, valid_in_patch)
+    again = _run_metrics(pred, gt, mask_p, rows, valid_in_patch)
+    assert torch.equal(out, again), "two runs differ"
+    got = out.cpu().numpy().astype(np.float64)
+    err, err32 = np.abs(got - want), np.abs(f32 - want)
+    bound = np.maximum(1e-6 * np.abs(want), 4.0 * err32)
+    report = (f"Hg x Wg = {hg}x{wg}, valid_in_patch = {valid_in_patch}, mask = {with_mask}: kernel error epe {err[:, 0].max():.2e} "
+              f"cos {err[:, 1].max():.2e}; float32 torch error epe {err32[:, 0].max():.2e} cos {err32[:, 1].max():.2e}; "
+              f"values epe {want[:, 0].tolist()} cos {want[:, 1].tolist()}")
+    print(report)
+    assert (err <= bound).all(), report
+    if with_mask:                              # the patch changes the metrics: the blend is not a no-op here
+        plain = _restated_metrics(pred, gt, None, rows, valid_in_patch, torch.float64)
+        assert np.abs(plain - want).max() > 1e-3
+
+
+# ------------------------------------------------------------------------------------------------------------------ 3. windowed
+def test_windowed_path_equals_generic_path(net, scene, generic):
+    res_g, flows_g = generic
+    res_w, flows_w = _sweep(net, scene, chunk=5, cone=True)
+    assert res_w.windowed and not res_g.windowed
+    assert len(res_w.locations) == 32 and res_w.adv_epe.shape == (4, 8)
+    scale = float(flows_g.abs().max())
+    diff = float((flows_w - flows_g).abs().max())
+    print(f"windowed vs generic flows: {diff / scale:.2e} of max |flow| = {scale:.3e}")
+    assert diff <= 1e-5 * scale, f"{diff / scale:.2e} of max |flow|"
+    _assert_maps(res_w, res_g.adv_epe, res_g.adv_cos_sim, "windowed vs generic")
+    assert abs(res_w.epe - res_g.epe) <= 1e-4 * abs(res_g.epe) and abs(res_w.cos_sim - res_g.cos_sim) <= 1e-4
+    # the comparison discriminates: the positions differ from each other by more than the maps may differ between the paths
+    assert float(np.ptp(res_g.adv_epe)) > 3e-4 * res_g.epe and float(np.abs(res_g.adv_epe - res_g.epe).min()) > 3e-4 * res_g.epe
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4. literal loop
+def test_generic_path_equals_the_literal_loop(net, scene, generic):
+    res, _ = generic
+    tgt, ref, gt, patch, mask = scene
+    adv_epe, adv_cos, epe, cos_sim, worst = _literal_loop(net, ARGS, tgt, ref, gt, patch, mask, STRIDE)
+    assert res.adv_epe.shape == adv_epe.shape == (4, 8) and res.adv_epe.dtype == np.float64
+    _assert_maps(res, adv_epe, adv_cos, "generic vs literal loop")
+    assert abs(res.epe - epe) <= 1e-4 * abs(epe), (res.epe, epe)
+    assert abs(res.cos_sim - cos_sim) <= 1e-4, (res.cos_sim, cos_sim)
+    assert res.worst == worst
+    assert res.locations[:5] == [(0, 0), (32, 0), (64, 0), (96, 0), (0, 32)]
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5. PWC-Net
+def test_second_network_on_the_generic_path():
+    from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
+    from understanding_flow_robustness_amd.patch_sweep import sweep_patch_locations
+    args = Namespace(flownet="PWCNet", norotate=True)
+    pwc = fetch_model(args, synthetic_seed=0).to(DEV)
+    g = torch.Generator().manual_seed(43)
+    tgt, ref = torch.rand(1, 3, 128, 192, generator=g).to(DEV), torch.rand(1, 3, 128, 192, generator=g).to(DEV)
+    gt = torch.cat((torch.randn(1, 2, 120, 180, generator=g) * 3.0, (torch.rand(1, 1, 120, 180, generator=g) > 0.3).float()), 1).to(DEV)
+    patch, mask = np.random.RandomState(6).rand(1, 3, 16, 16), _disc(16)
+    res = sweep_patch_locations(pwc, tgt, ref, gt, patch, mask, args, stride=48, chunk=4)
+    assert not res.windowed and res.adv_epe.shape == (3, 4)
+    with pytest.raises(RuntimeError, match="windowed path cannot serve"):
+        sweep_patch_locations(pwc, tgt, ref, gt, patch, mask, args, stride=48, chunk=4, cone=True)
+    adv_epe, adv_cos, epe, cos_sim, worst = _literal_loop(pwc, args, tgt, ref, gt, patch, mask, 48)
+    _assert_maps(res, adv_epe, adv_cos, "PWC-Net, generic vs literal loop")
+    assert abs(res.epe - epe) <= 1e-4 * abs(epe) and abs(res.cos_sim - cos_sim) <= 1e-4
+    assert res.worst == worst
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. state
+def test_sweep_leaves_the_shared_engine_as_the_attack_steps_expect(net, scene):
+    """chunk = 1: the sweep runs on the engine of the batch-1 attack step.  The attack produces the same patch before and after a
+    sweep, two sweeps give identical maps, and the engine holds the clean features afterwards."""
+    from understanding_flow_robustness_amd.flownetc_engine import get_engine
+    from understanding_flow_robustness_amd.flownets.utils_model import predict_flow
+    from understanding_flow_robustness_amd.patch_attack import attack
+    tgt, ref, gt, patch, mask = scene
+    canvas_mask = torch.zeros(1, 3, H, W, **F32)
+    canvas_mask[:, :, 40:40 + S, 100:100 + S] = torch.from_numpy(mask).to(DEV)
+    g = torch.Generator().manual_seed(3)
+    patch0 = torch.rand(1, 3, H, W, generator=g).to(DEV) * canvas_mask
+    with torch.no_grad():
+        target = -predict_flow(net, None, tgt, ref, ARGS)
+
+    def attacked():
+        p = patch0.clone()
+        a_t, _, a_r, p = attack(net, tgt, None, ref, p, canvas_mask, patch0, target, None, args=ARGS)
+        return p.clone(), a_t
+    before, adv_before = attacked()
+    assert float((before - patch0).abs().max()) > 0.0
+    first, _ = _sweep(net, scene, chunk=1, cone=True)
+    second, _ = _sweep(net, scene, chunk=1, cone=True)
+    assert first.windowed and np.array_equal(first.adv_epe, second.adv_epe) and np.array_equal(first.adv_cos_sim, second.adv_cos_sim)
+    assert first.worst == second.worst and (first.epe, first.cos_sim) == (second.epe, second.cos_sim)
+    eng = get_engine(net, 1, H, W, torch.device(DEV))
+    with torch.no_grad():
+        c2, c3 = net.encode(torch.cat((tgt, ref), 0))
+        assert torch.equal(eng.c3_nchw, c3[:2])
+    after, adv_after = attacked()
+    assert torch.equal(after, before) and torch.equal(adv_after, adv_before)

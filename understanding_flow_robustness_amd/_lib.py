@@ -270,6 +270,8 @@ SIGNATURES = {
     "ufr_train_loss": [C.POINTER(TrainLossDesc), _vp],
     "ufr_grad_norm": [C.POINTER(AdamwSeg), _i, _f, _vp, _l, _vp, _vp],
     "ufr_adamw_step": [C.POINTER(AdamwSeg), _i, C.POINTER(AdamwHyper), _vp, _vp],
+    "ufr_sweep_paste": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, C.POINTER(ConeChain), _i, _i, _vp, _vp, _vp],
+    "ufr_sweep_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
 }
 PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_device_count": (C.c_int, []), "ufr_build_manifest": (C.c_char_p, []),
@@ -280,7 +282,8 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_pwc_warp_backward_workspace_bytes": (C.c_long, [_i, _i, _i]),
          "ufr_altcorr_pyramid_workspace_bytes": (C.c_long, [_i, _i, _i, _i, _i, _i]),
          "ufr_train_loss_workspace_doubles": (C.c_long, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-         "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i])}
+         "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i]),
+         "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i])}
 
 
 def lib():

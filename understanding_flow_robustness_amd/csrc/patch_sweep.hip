@@ -1,0 +1,392 @@
+// patch_sweep.hip -- the patch location sweep of patch_attacks/test_moving_patch.py:299-445 (gfx950): the finished patch is moved
+// over ONE clean frame pair and the end-point error / cosine similarity against the blended ground truth is recorded per position.
+// Two streaming entries serve a chunk of K positions:
+//   ufr_sweep_paste    the K adversarial pairs from the one clean pair -- as canvases [K,3,H,W], or, for the windowed prefix, only
+//                      the window around each position's patch (the window table of ufr_cone_window first, then the windows);
+//   ufr_sweep_metrics  resized prediction, resized canvas mask, blended ground truth, both metrics and their weighted means in one
+//                      pass over the ground-truth pixels; float64 throughout, workgroup partials + a finalize launch (the pattern of
+//                      train_loss.hip): no float atomics, two runs are bit-identical.
+// The reference does, per position: three canvas-sized host arrays, one H2D copy, five torch operators for the paste, a bilinear
+// resize of the mask, five for the blend, two metric calls that each end in `.item()`.
+#include <climits>
+#include <cstdint>
+
+#include "ufr_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kSlots = 128;            // workgroups (= partials) per position at most
+constexpr int kSums = 3;               // valid * epe, valid * cos, valid
+constexpr int kWinInts = 8;            // win[k] = {y0, x0, need_h, need_w, ymin, ymax, xmin, xmax} (window.hip)
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// attack.hip's paste_placed_kernel, do_clamp = 1: (1-m)*img and m*patch are rounded separately, then added (no fma)
+__device__ __forceinline__ float paste_clamped(float img, float m, float pv, float lo, float hi) {
+  const float mp = m * pv, om = 1.0f - m;
+  return clampf(om * img + mp, lo, hi);
+}
+
+// ---- canvas form: idx runs over [K,3,H,W] in units of V floats; the clean pair is [3,H,W] ---------------------------------------
+template <int V>
+__global__ __launch_bounds__(kBlock) void sweep_paste_canvas_kernel(const float* __restrict__ tgt, const float* __restrict__ ref,
+                                                                    const float* __restrict__ patch_p, const float* __restrict__ mask_p,
+                                                                    const int* __restrict__ origins, float* __restrict__ adv_tgt,
+                                                                    float* __restrict__ adv_ref, long total, int H, int W, int ph,
+                                                                    int pw, float lo, float hi) {
+  const long HW = (long)H * W, CHW = 3 * HW;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long idx = q * V;
+    const int k = (int)(idx / CHW);
+    const long src = idx - (long)k * CHW;
+    const int c = (int)(src / HW);
+    const long pix = src - (long)c * HW;
+    const int y = (int)(pix / W), x = (int)(pix - (long)y * W);
+    const int i = y - origins[2 * k], j0 = x - origins[2 * k + 1];
+    float t[V], r[V];
+    if constexpr (V == 4) {
+      const float4 tv = *reinterpret_cast<const float4*>(tgt + src), rv = *reinterpret_cast<const float4*>(ref + src);
+      t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+      r[0] = rv.x; r[1] = rv.y; r[2] = rv.z; r[3] = rv.w;
+    } else {
+      t[0] = tgt[src];
+      r[0] = ref[src];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int j = j0 + v;
+      float m = 0.f, pv = 0.f;
+      if ((unsigned)i < (unsigned)ph && (unsigned)j < (unsigned)pw) {
+        const int e = (c * ph + i) * pw + j;
+        m = mask_p[e];
+        pv = patch_p[e];
+      }
+      t[v] = paste_clamped(t[v], m, pv, lo, hi);
+      r[v] = paste_clamped(r[v], m, pv, lo, hi);
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(adv_tgt + idx) = make_float4(t[0], t[1], t[2], t[3]);
+      *reinterpret_cast<float4*>(adv_ref + idx) = make_float4(r[0], r[1], r[2], r[3]);
+    } else {
+      adv_tgt[idx] = t[0];
+      adv_ref[idx] = r[0];
+    }
+  }
+}
+
+// ---- window form, first launch: the window table ------------------------------------------------------------------------------
+__device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
+__device__ __forceinline__ int ceil_div_i(int a, int b) { return -floor_div(-a, b); }
+
+// window.hip's cone_axis, statement for statement (ufr_cone_window and ufr_attack_place run it; the tests compare the tables bit for
+// bit): [lo, hi] (input pixels, inclusive) -> window origin / needed extent in pixels.
+__device__ void cone_axis(int lo, int hi, int size, const ufr_cone_chain& ch, int win, int* origin, int* need) {
+  int total = 1;
+  for (int l = 0; l < ch.n_layers; ++l) total *= ch.stride[l];
+  const int cells = size / total;
+  if (hi < lo) { *origin = 0; *need = 0; return; }
+  int need_lo = INT_MAX, need_hi = -1, n = size, jump = 1, t = 0;
+  for (int l = 0; l < ch.n_layers; ++l) {
+    const int k = ch.kernel[l], s = ch.stride[l], p = ch.pad[l];
+    const int n_out = (n + 2 * p - k) / s + 1;
+    lo = max(ceil_div_i(lo + p - (k - 1), s), 0);
+    hi = min(floor_div(hi + p, s), n_out - 1);
+    n = n_out; jump *= s;
+    while (t < ch.n_taps && ch.tap_layer[t] == l) {
+      const int per = total / jump;
+      need_lo = min(need_lo, floor_div(lo - ch.tap_margin[t], per));
+      need_hi = max(need_hi, floor_div(hi + ch.tap_margin[t], per));
+      ++t;
+    }
+  }
+  need_lo = max(need_lo, 0); need_hi = min(need_hi, cells - 1);
+  const int cnt = need_hi - need_lo + 1, wcells = win / total;
+  int o = need_lo - max(wcells - cnt, 0) / 2;
+  o = min(max(o, 0), max(cells - wcells, 0));
+  *origin = o * total; *need = cnt * total;
+}
+
+// One workgroup: the box of mask_p != 0 (all channels), then per position the table ufr_cone_window computes from the canvas mask,
+// whose box is origin + that box (the host has checked that every placement lies inside the frame).
+__global__ __launch_bounds__(kBlock) void sweep_window_table_kernel(const float* __restrict__ mask_p, const int* __restrict__ origins,
+                                                                    int* __restrict__ win, int K, int H, int W, int ph, int pw,
+                                                                    const ufr_cone_chain ch, int win_h, int win_w) {
+  __shared__ int box[4];       // imin, imax, jmin, jmax
+  const int tid = threadIdx.x, n = 3 * ph * pw, plane = ph * pw;
+  if (tid == 0) { box[0] = INT_MAX; box[1] = -1; box[2] = INT_MAX; box[3] = -1; }
+  __syncthreads();
+  int imin = INT_MAX, imax = -1, jmin = INT_MAX, jmax = -1;
+  for (int e = tid; e < n; e += kBlock) {
+    if (mask_p[e] != 0.f) {
+      const int r = e % plane, i = r / pw, j = r - i * pw;
+      imin = min(imin, i); imax = max(imax, i); jmin = min(jmin, j); jmax = max(jmax, j);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    imin = min(imin, __shfl_xor(imin, o)); imax = max(imax, __shfl_xor(imax, o));
+    jmin = min(jmin, __shfl_xor(jmin, o)); jmax = max(jmax, __shfl_xor(jmax, o));
+  }
+  if ((tid & 63) == 0 && imax >= 0) {      // integer min / max in LDS: exact in any order
+    atomicMin(&box[0], imin); atomicMax(&box[1], imax); atomicMin(&box[2], jmin); atomicMax(&box[3], jmax);
+  }
+  __syncthreads();
+  for (int k = tid; k < K; k += kBlock) {
+    const int oy = origins[2 * k], ox = origins[2 * k + 1];
+    int ymin = INT_MAX, ymax = -1, xmin = INT_MAX, xmax = -1;
+    if (box[1] >= 0) { ymin = oy + box[0]; ymax = oy + box[1]; xmin = ox + box[2]; xmax = ox + box[3]; }
+    int* w = win + k * kWinInts;
+    w[4] = ymin; w[5] = ymax; w[6] = xmin; w[7] = xmax;
+    int o0, o1, n0, n1;
+    cone_axis(ymin, ymax, H, ch, win_h, &o0, &n0);
+    cone_axis(xmin, xmax, W, ch, win_w, &o1, &n1);
+    w[0] = o0; w[1] = o1; w[2] = n0; w[3] = n1;
+  }
+}
+
+// ---- window form, second launch: xw [2K,3,wh,ww] = windows of the K pasted first frames, then of the K pasted second frames -------
+// q runs over [K,3,wh,ww] in units of V floats; both frames of a position leave the same thread (one mask / patch lookup).
+template <int V>
+__global__ __launch_bounds__(kBlock) void sweep_paste_window_kernel(const float* __restrict__ tgt, const float* __restrict__ ref,
+                                                                    const float* __restrict__ patch_p, const float* __restrict__ mask_p,
+                                                                    const int* __restrict__ origins, const int* __restrict__ win,
+                                                                    float* __restrict__ xw, long total, int K, int H, int W, int wh,
+                                                                    int ww, int ph, int pw, float lo, float hi) {
+  const long HW = (long)H * W, whw = (long)wh * ww, half = (long)K * 3 * whw;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long e = q * V;
+    const int k = (int)(e / (3 * whw));
+    const long r = e - (long)k * 3 * whw;
+    const int c = (int)(r / whw);
+    const long wp = r - (long)c * whw;
+    const int ii = (int)(wp / ww), jj = (int)(wp - (long)ii * ww);
+    const int* w = win + k * kWinInts;
+    // clamped like ufr_window_gather_pair: the window always lies inside the frame
+    const int y0 = min(max(w[0], 0), H - wh), x0 = min(max(w[1], 0), W - ww);
+    const int y = y0 + ii, x = x0 + jj;
+    const long src = (long)c * HW + (long)y * W + x;
+    const int i = y - origins[2 * k], j0 = x - origins[2 * k + 1];
+    float t[V], s[V];
+    if constexpr (V == 4) {          // x0 is a multiple of the chain's total stride (a multiple of 4, checked by the host) or W - ww
+      const float4 tv = *reinterpret_cast<const float4*>(tgt + src), rv = *reinterpret_cast<const float4*>(ref + src);
+      t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+      s[0] = rv.x; s[1] = rv.y; s[2] = rv.z; s[3] = rv.w;
+    } else {
+      t[0] = tgt[src];
+      s[0] = ref[src];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int j = j0 + v;
+      float m = 0.f, pv = 0.f;
+      if ((unsigned)i < (unsigned)ph && (unsigned)j < (unsigned)pw) {
+        const int pe = (c * ph + i) * pw + j;
+        m = mask_p[pe];
+        pv = patch_p[pe];
+      }
+      t[v] = paste_clamped(t[v], m, pv, lo, hi);
+      s[v] = paste_clamped(s[v], m, pv, lo, hi);
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(xw + e) = make_float4(t[0], t[1], t[2], t[3]);
+      *reinterpret_cast<float4*>(xw + half + e) = make_float4(s[0], s[1], s[2], s[3]);
+    } else {
+      xw[e] = t[0];
+      xw[half + e] = s[0];
+    }
+  }
+}
+
+// ---- metrics ------------------------------------------------------------------------------------------------------------------
+// the sum over the workgroup in a fixed order, returned to every thread (train_loss.hip)
+__device__ inline double block_sum(double v, double* lds) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  __syncthreads();                                            // the previous use of lds is over
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int i = 0; i < kBlock / 64; ++i) t += lds[i];
+  return t;
+}
+
+// torch's upsample_bilinear2d, align_corners = False, size given (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index):
+//   src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out;  i0 = (int)src;  i1 = i0 + (i0 < in - 1);  l1 = src - i0
+// in float64: with in == out the source is dst itself and l1 = 0
+__device__ __forceinline__ void bilinear_source(int dst, double scale, int in, int& i0, int& i1, double& l1) {
+  const double src = fmax(scale * ((double)dst + 0.5) - 0.5, 0.0);
+  i0 = min((int)src, in - 1);
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = src - (double)i0;
+}
+
+__device__ __forceinline__ double bilinear(double v00, double v01, double v10, double v11, double ly, double lx) {
+  const double hy = 1.0 - ly, hx = 1.0 - lx;
+  return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
+// grid (slots, K): workgroup (s, k) walks the ground-truth pixels s * 256 + t, + slots * 256, ... of position k
+__global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                               const float* __restrict__ mask_p, const int* __restrict__ origins,
+                                                               int H, int W, int Hg, int Wg, int ph, int pw, double patch_valid,
+                                                               double* __restrict__ part) {
+  __shared__ double lds[kBlock / 64];
+  const int k = blockIdx.y;
+  const long HW = (long)H * W, HWg = (long)Hg * Wg;
+  const float* __restrict__ pu = pred + (long)k * 2 * HW;
+  const float* __restrict__ pv = pu + HW;
+  const double sy = (double)H / (double)Hg, sx = (double)W / (double)Wg;
+  const double scale_u = (double)Wg / (double)W, scale_v = (double)Hg / (double)H;     // losses.py:27
+  int oy = 0, ox = 0;
+  if (mask_p != nullptr) { oy = origins[2 * k]; ox = origins[2 * k + 1]; }
+  double sum[kSums] = {0.0, 0.0, 0.0};
+  for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
+    const int yg = (int)(p / Wg), xg = (int)(p - (long)yg * Wg);
+    int y0, y1, x0, x1;
+    double ly, lx;
+    bilinear_source(yg, sy, H, y0, y1, ly);
+    bilinear_source(xg, sx, W, x0, x1, lx);
+    const long r0 = (long)y0 * W, r1 = (long)y1 * W;
+    const double fu = bilinear((double)pu[r0 + x0], (double)pu[r0 + x1], (double)pu[r1 + x0], (double)pu[r1 + x1], ly, lx);
+    const double fv = bilinear((double)pv[r0 + x0], (double)pv[r0 + x1], (double)pv[r1 + x0], (double)pv[r1 + x1], ly, lx);
+    double g[3] = {(double)gt[p], (double)gt[HWg + p], (double)gt[2 * HWg + p]};
+    if (mask_p != nullptr) {
+      // the canvas mask at the (already clamped) source rows / columns: mask_p inside the rectangle, 0 outside
+      const int i0 = y0 - oy, i1 = y1 - oy, j0 = x0 - ox, j1 = x1 - ox;
+      const bool a0 = (unsigned)i0 < (unsigned)ph, a1 = (unsigned)i1 < (unsigned)ph;
+      const bool b0 = (unsigned)j0 < (unsigned)pw, b1 = (unsigned)j1 < (unsigned)pw;
+      if ((a0 || a1) && (b0 || b1)) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float* __restrict__ mc = mask_p + (long)c * ph * pw;
+          const double m00 = a0 && b0 ? (double)mc[i0 * pw + j0] : 0.0, m01 = a0 && b1 ? (double)mc[i0 * pw + j1] : 0.0;
+          const double m10 = a1 && b0 ? (double)mc[i1 * pw + j0] : 0.0, m11 = a1 && b1 ? (double)mc[i1 * pw + j1] : 0.0;
+          const double m = bilinear(m00, m01, m10, m11, ly, lx);
+          g[c] = (1.0 - m) * g[c] + m * (c == 2 ? patch_valid : 0.0);            // test_moving_patch.py:430-432
+        }
+      }
+    }
+    const double du = g[0] - fu * scale_u, dv = g[1] - fv * scale_v;              // losses.py:29-30
+    const double epe = sqrt(du * du + dv * dv);
+    // torch.nn.functional.cosine_similarity: each vector divided by max(its norm, eps) first, then the dot product
+    const double ng = fmax(sqrt(g[0] * g[0] + g[1] * g[1]), 1e-8), nf = fmax(sqrt(fu * fu + fv * fv), 1e-8);
+    const double cs = (g[0] / ng) * (fu / nf) + (g[1] / ng) * (fv / nf);
+    sum[0] += epe * g[2];
+    sum[1] += cs * g[2];
+    sum[2] += g[2];
+  }
+  for (int q = 0; q < kSums; ++q) {
+    const double t = block_sum(sum[q], lds);
+    if (threadIdx.x == 0) part[((long)k * kSlots + blockIdx.x) * kSums + q] = t;
+  }
+}
+
+// grid K: one workgroup adds the `slots` partials of its position in a fixed order
+__global__ __launch_bounds__(kBlock) void sweep_metrics_finalize_kernel(const double* __restrict__ part, int slots,
+                                                                        float* __restrict__ out) {
+  __shared__ double lds[kBlock / 64];
+  const int k = blockIdx.x;
+  double t[kSums];
+  for (int q = 0; q < kSums; ++q)
+    t[q] = block_sum((int)threadIdx.x < slots ? part[((long)k * kSlots + threadIdx.x) * kSums + q] : 0.0, lds);
+  if (threadIdx.x == 0) {
+    const double den = t[2] + 1e-8;                                               // losses.py:22
+    out[2 * k] = (float)(t[0] / den);
+    out[2 * k + 1] = (float)(t[1] / den);
+  }
+}
+
+int check_origins(const char* what, const int* origins_host, int K, int H, int W, int ph, int pw) {
+  for (int k = 0; k < K; ++k)
+    UFR_REQUIRE(origins_host[2 * k] >= 0 && origins_host[2 * k] + ph <= H && origins_host[2 * k + 1] >= 0 &&
+                    origins_host[2 * k + 1] + pw <= W,
+                "%s: placement %d = (%d, %d) of the %dx%d patch leaves the %dx%d frame", what, k, origins_host[2 * k],
+                origins_host[2 * k + 1], ph, pw, H, W);
+  return UFR_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int ufr_sweep_paste(const float* tgt, const float* ref, const float* patch_p, const float* mask_p, const int* origins,
+                               const int* origins_host, float* adv_tgt, float* adv_ref, int K, int H, int W, int ph, int pw, float lo,
+                               float hi, const ufr_cone_chain* chain, int win_h, int win_w, int* win, float* xw, ufr_stream_t stream) {
+  UFR_REQUIRE(tgt && ref && patch_p && mask_p && origins, "sweep paste: null pointer argument");
+  UFR_REQUIRE(origins_host, "sweep paste: the origins are needed on the host too (every placement is checked before the launch)");
+  UFR_REQUIRE(K > 0 && H > 0 && W > 0 && ph > 0 && pw > 0, "sweep paste: bad shape K=%d H=%d W=%d ph=%d pw=%d", K, H, W, ph, pw);
+  UFR_REQUIRE(ph <= H && pw <= W, "sweep paste: the %dx%d patch is larger than the %dx%d frame", ph, pw, H, W);
+  UFR_REQUIRE((long)K * 3 * H * W < (1L << 40) && (long)3 * ph * pw < (1L << 30), "sweep paste: too many pixels");
+  UFR_REQUIRE(lo <= hi, "sweep paste: empty pixel range [%g, %g]", (double)lo, (double)hi);
+  if (int rc = check_origins("sweep paste", origins_host, K, H, W, ph, pw)) return rc;
+  hipStream_t st = ufr::as_stream(stream);
+  if (win == nullptr) {
+    UFR_REQUIRE(chain == nullptr && xw == nullptr, "sweep paste: a chain or window stack without the window table");
+    UFR_REQUIRE(adv_tgt && adv_ref, "sweep paste: null pointer argument (canvas form: adv_tgt, adv_ref)");
+    const long total = (long)K * 3 * H * W;
+    if (W % 4 == 0 && aligned16(tgt) && aligned16(ref) && aligned16(adv_tgt) && aligned16(adv_ref))
+      sweep_paste_canvas_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(tgt, ref, patch_p, mask_p, origins, adv_tgt,
+                                                                                         adv_ref, total / 4, H, W, ph, pw, lo, hi);
+    else
+      sweep_paste_canvas_kernel<1><<<ufr::stream_grid(total, kBlock), kBlock, 0, st>>>(tgt, ref, patch_p, mask_p, origins, adv_tgt,
+                                                                                     adv_ref, total, H, W, ph, pw, lo, hi);
+    return ufr::launched("sweep_paste_canvas_kernel");
+  }
+  UFR_REQUIRE(chain != nullptr, "sweep paste: the window form needs the chain");
+  UFR_REQUIRE(xw != nullptr, "sweep paste: the window form needs the window stack xw");
+  UFR_REQUIRE(chain->n_layers > 0 && chain->n_layers <= UFR_MAX_CONE_LAYERS && chain->n_taps > 0 &&
+                  chain->n_taps <= UFR_MAX_CONE_LAYERS, "sweep paste: bad chain");
+  int stride = 1;
+  for (int l = 0; l < chain->n_layers; ++l) {
+    UFR_REQUIRE(chain->kernel[l] > 0 && chain->stride[l] > 0 && chain->pad[l] >= 0, "sweep paste: bad layer %d", l);
+    stride *= chain->stride[l];
+  }
+  for (int t = 0; t < chain->n_taps; ++t)
+    UFR_REQUIRE(chain->tap_layer[t] >= 0 && chain->tap_layer[t] < chain->n_layers &&
+                    (t == 0 || chain->tap_layer[t] >= chain->tap_layer[t - 1]) && chain->tap_margin[t] >= 0,
+                "sweep paste: taps must be sorted by layer");
+  UFR_REQUIRE(H % stride == 0 && W % stride == 0, "sweep paste: %dx%d is not a multiple of the chain stride %d", H, W, stride);
+  UFR_REQUIRE(win_h > 0 && win_w > 0 && win_h % stride == 0 && win_w % stride == 0 && win_h <= H && win_w <= W,
+              "sweep paste: window %dx%d must be a multiple of %d inside %dx%d", win_h, win_w, stride, H, W);
+  sweep_window_table_kernel<<<1, kBlock, 0, st>>>(mask_p, origins, win, K, H, W, ph, pw, *chain, win_h, win_w);
+  if (int rc = ufr::launched("sweep_window_table_kernel")) return rc;
+  const long total = (long)K * 3 * win_h * win_w;
+  // a window's first column is a multiple of the chain stride, or W - win_w when the clamp holds it inside the frame
+  if (W % 4 == 0 && win_w % 4 == 0 && stride % 4 == 0 && aligned16(tgt) && aligned16(ref) && aligned16(xw))
+    sweep_paste_window_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(tgt, ref, patch_p, mask_p, origins, win, xw,
+                                                                                       total / 4, K, H, W, win_h, win_w, ph, pw, lo, hi);
+  else
+    sweep_paste_window_kernel<1><<<ufr::stream_grid(total, kBlock), kBlock, 0, st>>>(tgt, ref, patch_p, mask_p, origins, win, xw, total,
+                                                                                   K, H, W, win_h, win_w, ph, pw, lo, hi);
+  return ufr::launched("sweep_paste_window_kernel");
+}
+
+extern "C" long ufr_sweep_metrics_workspace_doubles(int K) { return K < 1 ? -1 : (long)K * kSlots * kSums; }
+
+extern "C" int ufr_sweep_metrics(const float* pred, const float* gt, const float* mask_p, const int* origins, const int* origins_host,
+                                 int K, int H, int W, int Hg, int Wg, int ph, int pw, int valid_in_patch, double* ws, long ws_elems,
+                                 float* out, int row0, int rows, ufr_stream_t stream) {
+  UFR_REQUIRE(pred && gt && ws && out, "sweep metrics: null pointer argument");
+  UFR_REQUIRE(K > 0 && K <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0, "sweep metrics: bad shape K=%d H=%d W=%d Hg=%d Wg=%d", K, H,
+              W, Hg, Wg);
+  UFR_REQUIRE((long)H * W < (1L << 30) && (long)Hg * Wg < (1L << 30), "sweep metrics: too many pixels");
+  UFR_REQUIRE(valid_in_patch == 0 || valid_in_patch == 1, "sweep metrics: valid_in_patch = %d (0 or 1)", valid_in_patch);
+  UFR_REQUIRE(row0 >= 0 && rows > 0 && (long)row0 + K <= rows, "sweep metrics: rows %d .. %ld leave the result buffer of %d rows", row0,
+              (long)row0 + K - 1, rows);
+  UFR_REQUIRE(ws_elems >= ufr_sweep_metrics_workspace_doubles(K), "sweep metrics: workspace of %ld doubles, %ld needed", ws_elems,
+              ufr_sweep_metrics_workspace_doubles(K));
+  if (mask_p != nullptr) {
+    UFR_REQUIRE(origins && origins_host, "sweep metrics: null pointer argument (a patch needs its origins, on the device and the host)");
+    UFR_REQUIRE(ph > 0 && pw > 0, "sweep metrics: bad shape ph=%d pw=%d", ph, pw);
+    UFR_REQUIRE(ph <= H && pw <= W && (long)3 * ph * pw < (1L << 30), "sweep metrics: the %dx%d patch is larger than the %dx%d frame",
+                ph, pw, H, W);
+    if (int rc = check_origins("sweep metrics", origins_host, K, H, W, ph, pw)) return rc;
+  }
+  hipStream_t st = ufr::as_stream(stream);
+  const long npix = (long)Hg * Wg;
+  int slots = ufr::ceil_div(npix, kBlock);
+  if (slots > kSlots) slots = kSlots;
+  sweep_metrics_kernel<<<dim3(slots, K), kBlock, 0, st>>>(pred, gt, mask_p, origins, H, W, Hg, Wg, ph, pw, (double)valid_in_patch, ws);
+  if (int rc = ufr::launched("sweep_metrics_kernel")) return rc;
+  sweep_metrics_finalize_kernel<<<K, kBlock, 0, st>>>(ws, slots, out + 2L * row0);
+  return ufr::launched("sweep_metrics_finalize_kernel");
+}

@@ -814,6 +814,16 @@ int ufr_corr_forward_planes_window(const void* f1_planes, const void* f2_planes,
                                    int dilation_patch, float scale, float slope, const int* win, int level_stride,
                                    int win_cells, ufr_stream_t stream);
 
+/* ufr_corr_forward_planes on the entries that can have changed when the features changed only inside each sample's rectangle:
+ * the window at (win[b*8 + 0], win[b*8 + 1]) / level_stride, clamped into the frame, win_cells_h x win_cells_w cells (at most 23
+ * across), trimmed by `margin` cells on every edge that is not a frame edge (ufr_window_features_planes' rule; margin 0 = the
+ * whole window).  Afterwards every entry whose cell (y, x) or whose source cell (y + 2(dy-10), x + 2(dx-10)) lies in the
+ * rectangle holds the bits ufr_corr_forward_planes writes for the same features; every other entry keeps its value. */
+int ufr_corr_forward_planes_changed(const void* f1_planes, const void* f2_planes, long in_plane_stride, void* out_planes,
+                                    long out_plane_stride, int out_chunk0, int B, int C, int H, int W, int patch,
+                                    int dilation_patch, float scale, float slope, const int* win, int level_stride,
+                                    int win_cells_h, int win_cells_w, int margin, ufr_stream_t stream);
+
 /* Both adjoints of FlowNetC's cost volume (correlation_cuda_kernel.cu:86-233; patch 21, dilation_patch 2, 256 channels) on
  * the cells of the prefix window, on the matrix cores (csrc/correlation_window_mfma.hip), fused with everything around it:
  * G = the engine's chunk-major float32 gradient sum of conv3_1's input (the cost volume's channels start at chunk

@@ -11,6 +11,12 @@
 // double-buffered (XOR-swizzled images like csrc/igemm.hip), and each wave multiplies its 16 columns against 3 tiles of 16 source columns
 // (j in [i0 - 16, i0 + 32): 44 % of the MFMA work lands inside the band), float32 = six bf16 products.
 // out channel d = dy * 21 + (j - i + 10); value = leaky(R / C).
+//
+// Three entry points: the full volume (ufr_corr_forward_planes), and two incremental forms for the later iterations of an
+// attack call, when the features changed inside the prefix window only -- every row and displacement of the 64 columns around
+// the window (ufr_corr_forward_planes_window: the full kernel on one column block, kept as the reference), and only the
+// entries whose cell or source cell lies in the window's rectangle (ufr_corr_forward_planes_changed, what the engine runs:
+// `corr_fwd_planes_changed_kernel` below, a quarter of the window form's time).  All three write the same bits.
 #include "ufr_common.h"
 
 namespace {
@@ -234,6 +240,172 @@ int launch_corr_planes(const __bf16* a, const __bf16* b, long in_plane_stride, _
   return UFR_OK;
 }
 
+// ---- the changed entries only ------------------------------------------------------------------------------------------
+// Between the iterations of a call the features change only inside a rectangle of cells (the prefix window without its
+// inexact rim: plane_layout.hip `window_features_kernel`), so out[d = (dy, dx), y, x] can change only where
+//   (A) (y, x) lies in the rectangle, or (B) its source cell (y2, x2) = (y + 2 (dy - 10), x + 2 (dx - 10)) does.
+// Per column parity the rectangle holds at most 12 columns, one 16-column tile S; everything they meet lies in the 32
+// same-parity columns from 10 left of them, two tiles D.  A wave owns one pair of rows, for both column parities:
+//   (A) row y of the rectangle:  S of f1's row y  against D of f2's row y2 -> the 21 dx of the rectangle's columns;
+//   (B) row y2 of the rectangle: D of f1's row y  against S of f2's row y2 -> the dx whose source column is in the rectangle
+//       (every y, the rectangle's rows too: their columns outside the rectangle are case B's alone; where both cases write
+//       an entry they write the same bits).
+// 2 of the window form's 6 tile products per (row, dy, parity), on 2 x (rows of the rectangle) instead of all H rows.
+// The fragments are 16-byte plane reads straight into registers (`load_fragment`): nothing is reused inside a wave, so nothing
+// is staged.  A cell's 32 channels are 64 B, so the same-parity columns of a fragment each sit in half a 128-byte line: a
+// wave reads BOTH parities back to back and uses every line it fetches, and the four waves of a workgroup take four rows of
+// the rectangle against ONE row of the other map (the D tiles, 2/3 of the lines).  Measured at 8 pairs of 48 x 160 cells, 16 x 16
+// windows, beside the window form's 183 us: 46 us (kernel trace; 53 between two events).  One parity per wave and the 21 dy
+// of one row per workgroup: 82 us between events; either form with the loads in the fragment's own lane order: 87 - 93 us;
+// loads a stage ahead of the MFMAs, 3 or 4 waves per SIMD, stores of all 16 x 21 slots or only of the entries there are:
+// no difference.
+// An entry's arithmetic is the full kernel's: chunks 0-3 into one accumulator and 4-7 into another, six products per chunk in
+// PROD order with f1 as A and f2 as B, lo + hi, x scale, LeakyReLU, split3 -- an MFMA result depends on its A row, its B column
+// and its accumulator only, so the bits are those of corr_fwd_planes_k2_kernel whatever the tiles are made of.
+constexpr int CH_WAVES = 4;                       // waves per workgroup = rows of the rectangle that share a row of the other map
+constexpr int CH_MAX_CELLS = 23;                  // window width: 12 same-parity columns + 2 x 10 reach = 32
+
+// 16 bytes per lane in load order (above) -> the MFMA fragment: lane (row, k group) takes the 16 bytes of lane 4 row + k group
+__device__ __forceinline__ bf16x8 load_fragment(const __bf16* src, int perm) {
+  typedef __attribute__((ext_vector_type(4))) int i32x4;
+  i32x4 v = *reinterpret_cast<const i32x4*>(src);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = __builtin_amdgcn_ds_bpermute(perm, v[k]);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// rowS / rowD: pixel index of the first cell of the rectangle's row / of the other map's row; row1: of f1's row (the output's)
+template <bool CASE_B>
+__device__ __forceinline__ void corr_changed_rows(const __bf16* __restrict__ f1, const __bf16* __restrict__ f2, long in_plane_stride,
+                                                  __bf16* __restrict__ out, long out_plane_stride, int out_chunk0, long M, int W,
+                                                  float scale, float slope, long rowS, long rowD, long row1, int rx0, int rx1, int dy,
+                                                  float* otile, int lane) {
+  const __bf16* zero = reinterpret_cast<const __bf16*>(corr_zero_page);
+  const int fr = lane & 15, g = lane >> 4;        // the lane's place in a fragment: tile row (a column of the map), k group
+  // a lane LOADS piece lane & 3 of column lane >> 2, so that four neighbouring lanes read one cell's 64 bytes (in the
+  // fragment's own order the 16 lanes of a group each read from another line: 87 us instead of 53), and the fragment is
+  // put in order by a lane permutation
+  const int lc = lane >> 2, perm = ((fr << 2) | g) << 2;
+  const __bf16* baseS = (CASE_B ? f2 : f1) + rowS * 32 + (lane & 3) * 8;
+  const __bf16* baseD = (CASE_B ? f1 : f2) + rowD * 32 + (lane & 3) * 8;
+  int i_lo[2], n[2];                              // per parity: the rectangle's columns are 2 i + par, i in [i_lo, i_lo + n)
+  bool s_ok[2], d_ok[2][2];
+  const __bf16 *sp[2], *dp[2][2];
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    i_lo[par] = (rx0 - par + 1) >> 1;
+    n[par] = ((rx1 - par + 1) >> 1) - i_lo[par];
+    s_ok[par] = lc < n[par];
+    sp[par] = baseS + (long)(2 * (i_lo[par] + lc) + par) * 32;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int u = i_lo[par] - R + 16 * t + lc, xu = 2 * u + par;
+      d_ok[par][t] = u >= 0 && xu < W;
+      dp[par][t] = baseD + (long)xu * 32;
+    }
+  }
+  f32x4 acc[2][2][2];                             // [half of the reduction][parity][D tile]
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) acc[h][par][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < KCH; ++c) {
+    const long off = (long)c * M * 32;
+    bf16x8 fs[2][3], fd[2][2][3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int par = 0; par < 2; ++par)           // the two parities of a line, one after the other
+        fs[par][p] = load_fragment(s_ok[par] ? sp[par] + p * in_plane_stride + off : zero, perm);
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+          fd[par][t][p] = load_fragment(d_ok[par][t] ? dp[par][t] + p * in_plane_stride + off : zero, perm);
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+#pragma unroll
+      for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          f32x4& a = acc[c / (KCH / 2)][par][t];
+          a = CASE_B ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[par][t][PROD_A[q]], fs[par][PROD_B[q]], a, 0, 0, 0)
+                     : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fs[par][PROD_A[q]], fd[par][t][PROD_B[q]], a, 0, 0, 0);
+        }
+  }
+  // through the wave's LDS tile [f1 column][dx], so that the 2-byte stores of a column's displacements are dense
+  constexpr int ROWS = 32;                        // case B: f1 columns of the two D tiles
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const float v = acc[0][par][t][rg] + acc[1][par][t][rg];
+        const int m = g * 4 + rg;                 // the result's A row, fr its B column
+        const int il = CASE_B ? 16 * t + m : m;
+        const int dx = CASE_B ? fr - il + 2 * R : 16 * t + fr - m;
+        if (dx >= 0 && dx < P && (!CASE_B || fr < n[par])) otile[il * OT + dx] = v;
+      }
+    // only the entries there are: (column of the rectangle, dx) in case A, (f1 column, source column in the rectangle) in case B
+    const int np = n[par], cnt = (CASE_B ? ROWS : P) * np;
+    for (int e = lane; e < cnt; e += 64) {
+      const int il = CASE_B ? e / np : e / P;
+      const int dx = CASE_B ? e - il * np - il + 2 * R : e - il * P;
+      const int i = CASE_B ? i_lo[par] - R + il : i_lo[par] + il, x = 2 * i + par;
+      if (!CASE_B || (dx >= 0 && dx < P && i >= 0 && x < W)) {
+        float v = otile[il * OT + dx] * scale;
+        v = v > 0.f ? v : v * slope;
+        __bf16 p0, p1, p2;
+        split3(v, p0, p1, p2);
+        const int d = dy * P + dx;
+        __bf16* o = out + ((long)(out_chunk0 + (d >> 5)) * M + row1 + x) * 32 + (d & 31);
+        o[0] = p0;
+        o[out_plane_stride] = p1;
+        o[2 * out_plane_stride] = p2;
+      }
+    }
+  }
+}
+
+// grid = B x 2 cases x H rows of the other map x groups of CH_WAVES same-parity rows of the window: sized for the largest
+// rectangle (a window in a frame corner), so a captured launch serves every placement; a wave whose row is not in its sample's
+// rectangle, or not within the reach of the other map's row, leaves at once.
+__global__ __launch_bounds__(64 * CH_WAVES, 3) void corr_fwd_planes_changed_kernel(
+    const __bf16* __restrict__ f1, const __bf16* __restrict__ f2, long in_plane_stride, __bf16* __restrict__ out, long out_plane_stride,
+    int out_chunk0, int B, int H, int W, float scale, float slope, const int* __restrict__ win, int level_stride, int wh, int ww,
+    int margin) {
+  __shared__ float tiles[CH_WAVES][32 * OT];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int groups = ((wh + 1) / 2 + CH_WAVES - 1) / CH_WAVES;
+  int item = blockIdx.x;
+  const int k = item % groups; item /= groups;
+  const int yd = item % H; item /= H;
+  const int case_b = item & 1, b = item >> 1;
+  if (b >= B) return;
+  // the rectangle: window_features_kernel's origin and rim rule
+  const int wy0 = min(max(win[b * 8 + 0] / level_stride, 0), H - wh), wx0 = min(max(win[b * 8 + 1] / level_stride, 0), W - ww);
+  const int ry0 = wy0 + (wy0 > 0 ? margin : 0), ry1 = wy0 + wh - (wy0 + wh < H ? margin : 0);
+  const int rx0 = wx0 + (wx0 > 0 ? margin : 0), rx1 = wx0 + ww - (wx0 + ww < W ? margin : 0);
+  const int ys = ry0 + ((ry0 ^ yd) & 1) + 2 * (k * CH_WAVES + wave);             // the rectangle's rows of yd's parity
+  const int dy = (case_b ? ys - yd : yd - ys) / 2 + R;                           // source row - row = 2 (dy - R)
+  if (ys >= ry1 || dy < 0 || dy >= P || rx1 <= rx0) return;
+  const long M = (long)B * H * W;
+  const long rowS = ((long)b * H + ys) * W, rowD = ((long)b * H + yd) * W;
+  if (case_b)
+    corr_changed_rows<true>(f1, f2, in_plane_stride, out, out_plane_stride, out_chunk0, M, W, scale, slope, rowS, rowD, rowD, rx0, rx1, dy,
+                            tiles[wave], lane);
+  else
+    corr_changed_rows<false>(f1, f2, in_plane_stride, out, out_plane_stride, out_chunk0, M, W, scale, slope, rowS, rowD, rowS, rx0, rx1, dy,
+                             tiles[wave], lane);
+}
+
 }  // namespace
 
 extern "C" int ufr_corr_forward_planes(const void* f1_planes, const void* f2_planes, long in_plane_stride, void* out_planes,
@@ -277,4 +449,24 @@ extern "C" int ufr_corr_forward_planes_window(const void* f1_planes, const void*
                                  ufr::as_stream(stream), win, level_stride);
   if (rc != UFR_OK) return rc;
   return ufr::launched("corr_fwd_planes_k2_kernel (window)");
+}
+
+extern "C" int ufr_corr_forward_planes_changed(const void* f1_planes, const void* f2_planes, long in_plane_stride, void* out_planes,
+                                               long out_plane_stride, int out_chunk0, int B, int C, int H, int W, int patch,
+                                               int dilation_patch, float scale, float slope, const int* win, int level_stride,
+                                               int win_cells_h, int win_cells_w, int margin, ufr_stream_t stream) {
+  UFR_REQUIRE(f1_planes && f2_planes && out_planes && win, "correlation (planes, changed): null pointer");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H < 65536 && out_chunk0 >= 0 && level_stride > 0 && win_cells_h > 0 &&
+                  win_cells_w > 0 && margin >= 0, "correlation (planes, changed): bad shape");
+  if (C != 32 * KCH || patch != P || dilation_patch != 2 || win_cells_w > CH_MAX_CELLS)
+    return ufr::fail(UFR_EUNSUPPORTED, "correlation (planes, changed): 256 channels, patch 21, dilation_patch 2, windows of at most "
+                                       "%d cells across; got C=%d patch=%d dilation_patch=%d cells=%d", CH_MAX_CELLS, C, patch,
+                     dilation_patch, win_cells_w);
+  UFR_REQUIRE(win_cells_h <= H && win_cells_w <= W && 2 * margin <= win_cells_h && 2 * margin <= win_cells_w,
+              "correlation (planes, changed): window %dx%d (margin %d) in a frame of %dx%d cells", win_cells_h, win_cells_w, margin, H, W);
+  const int groups = ufr::ceil_div((win_cells_h + 1) / 2, CH_WAVES);
+  corr_fwd_planes_changed_kernel<<<B * 2 * H * groups, 64 * CH_WAVES, 0, ufr::as_stream(stream)>>>(
+      static_cast<const __bf16*>(f1_planes), static_cast<const __bf16*>(f2_planes), in_plane_stride, static_cast<__bf16*>(out_planes),
+      out_plane_stride, out_chunk0, B, H, W, scale, slope, win, level_stride, win_cells_h, win_cells_w, margin);
+  return ufr::launched("corr_fwd_planes_changed_kernel");
 }

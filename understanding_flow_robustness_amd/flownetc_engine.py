@@ -99,6 +99,7 @@ class FlowNetCHeadEngine:
         self._prefix = None                                          # full-frame conv1-3 buffers + launches, built on first use
         self.flow_out, self.flow_scale = self.flow[2], float(getattr(net, "div_flow", 20.0))   # what the step's fused loss kernel reads
         self._wprefixes, self._wprefix = {}, None                    # window-prefix state per window size; the one used last
+        self._win_m3 = 0                         # conv3 rim of the last window patched into the planes (0: the whole window)
         self._build_launches()
 
     # ------------------------------------------------------------------------------------------------ set-up
@@ -343,6 +344,7 @@ class FlowNetCHeadEngine:
         lib, B, st = L.lib(), self.B, L.stream()
         h4, w4 = self.grid[4]
         h8, w8 = self.grid[8]
+        self._win_m3 = int(m3)
         L.check(lib.ufr_window_scatter_planes(L.ptr(c2_w), L.ptr(self.cat2.t), self.cat2.plane_stride, 0, L.ptr(win), B, B, 128,
                                               h4, w4, wh // 4, ww // 4, 4, m2, st), "window -> planes (conv2)")
         for k, dst in ((0, self.c3a_p), (1, self.c3b_p)):
@@ -436,6 +438,7 @@ class FlowNetCHeadEngine:
         (the window's conv2 as NCHW float32, which nothing on the attack's path reads) unwritten."""
         wh, ww = int(xw.shape[2]), int(xw.shape[3])
         P = self.window_prefix(wh, ww)
+        self._win_m3 = int(m3)
         self._conv1(P, xw.detach(), None)
         for _, launch, _ in P["fwd"]:
             launch()
@@ -714,15 +717,18 @@ class FlowNetCHeadEngine:
             self._pf_forward(k)
         return self.flow[2]
 
-    def forward_cached(self, band=None) -> torch.Tensor:
+    def forward_cached(self, band=None, corr_changed: bool = True) -> torch.Tensor:
         """`forward` on the features the engine already holds (prefix_full / load_prefix_features + scatter_window_features)."""
-        return self.forward(None, self._c3a, self._c3b, band)
+        return self.forward(None, self._c3a, self._c3b, band, corr_changed=corr_changed)
 
-    def forward(self, c2a: torch.Tensor | None, c3a: torch.Tensor, c3b: torch.Tensor, band=None) -> torch.Tensor:
+    def forward(self, c2a: torch.Tensor | None, c3a: torch.Tensor, c3b: torch.Tensor, band=None,
+                corr_changed: bool = True) -> torch.Tensor:
         """(conv2 of frame 1 [B,128,H/4,W/4], conv3 of both frames [B,256,H/8,W/8]) -> flow2 [B,2,H/4,W/4].
         `band` (band_conv.Band) with `incremental` set: the features differ from the previous call's only inside the
         prefix window, so conv_redir / conv3_1 / conv4 / conv4_1 recompute the band's columns only -- the plane buffers
-        still hold the previous iteration's activations everywhere else."""
+        still hold the previous iteration's activations everywhere else.  The cost volume then recomputes only the entries
+        whose cell or source cell lies in the window without its conv3 rim (`corr_changed`; False: every row and displacement
+        of the columns within the correlation's reach of the window, the comparison leg of tests/test_corr_changed_gpu.py)."""
         if not self.siamese:
             return self._forward_trunk(c2a, c3a)
         for t, name in ((c3a, "c3a"), (c3b, "c3b")):
@@ -741,10 +747,17 @@ class FlowNetCHeadEngine:
         # matrix cores, planes in, conv3_1's input planes out (correlation_planes.hip)
         if inc and band.cone_win is not None and band.cone_hw[1] // 8 <= 23:
             # later iterations of a call: only the window's neighbourhood of the volume changes
-            L.check(L.lib().ufr_corr_forward_planes_window(L.ptr(self.c3a_p.t), L.ptr(self.c3b_p.t), self.c3a_p.plane_stride,
-                                                           L.ptr(self.in31.t), self.in31.plane_stride, 1, self.B, 256, *self.grid[8],
-                                                           21, 2, 1.0 / 256.0, ig.LEAKY, L.ptr(band.cone_win), 8,
-                                                           band.cone_hw[1] // 8, L.stream()), "correlation forward (planes, window)")
+            if corr_changed:
+                L.check(L.lib().ufr_corr_forward_planes_changed(L.ptr(self.c3a_p.t), L.ptr(self.c3b_p.t), self.c3a_p.plane_stride,
+                                                                L.ptr(self.in31.t), self.in31.plane_stride, 1, self.B, 256, *self.grid[8],
+                                                                21, 2, 1.0 / 256.0, ig.LEAKY, L.ptr(band.cone_win), 8,
+                                                                band.cone_hw[0] // 8, band.cone_hw[1] // 8, self._win_m3, L.stream()),
+                        "correlation forward (planes, changed)")
+            else:
+                L.check(L.lib().ufr_corr_forward_planes_window(L.ptr(self.c3a_p.t), L.ptr(self.c3b_p.t), self.c3a_p.plane_stride,
+                                                               L.ptr(self.in31.t), self.in31.plane_stride, 1, self.B, 256, *self.grid[8],
+                                                               21, 2, 1.0 / 256.0, ig.LEAKY, L.ptr(band.cone_win), 8,
+                                                               band.cone_hw[1] // 8, L.stream()), "correlation forward (planes, window)")
         else:
             L.check(L.lib().ufr_corr_forward_planes(L.ptr(self.c3a_p.t), L.ptr(self.c3b_p.t), self.c3a_p.plane_stride,
                                                     L.ptr(self.in31.t), self.in31.plane_stride, 1, self.B, 256, *self.grid[8], 21, 2,

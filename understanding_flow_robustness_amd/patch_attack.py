@@ -80,12 +80,15 @@ class PatchAttackStep:
 
     def __init__(self, flow_net, args, batch, height, width, device="cuda:0", shared_patch=True,
                  exchange: ShardedExchange | None = None, use_graph=True, warmup=3, use_cone=None, patch_hw=None,
-                 sum_groups=1, skip_unread=True):
+                 sum_groups=1, skip_unread=True, corr_changed=True):
         L.lib()   # fail loudly, now, if libufr_hip.so is missing
         self.net, self.args = flow_net, args
         # the engine's banded backward writes gradients that only the band / the window reads where they are read
         # (flownetc_engine.py `backward`); False: every gradient sum in full
         self.skip_unread = bool(skip_unread)
+        # later iterations recompute only the cost-volume entries the window's features reach (flownetc_engine.py `forward`);
+        # False: every row and displacement of the columns around the window
+        self.corr_changed = bool(corr_changed)
         self.B, self.H, self.W = batch, height, width
         self.dev = torch.device(device)
         self.shared = shared_patch
@@ -351,7 +354,7 @@ class PatchAttackStep:
             else:
                 (_, m2, _, _, _), (_, m3, _, _, _) = self.taps
                 self.eng.window_prefix_forward(self.xw, self.win, m2, m3, c2_nchw=False)
-                self.eng.forward_cached(self.band)
+                self.eng.forward_cached(self.band, corr_changed=self.corr_changed)
             if self._fused_loss:                   # the loss kernel upsamples flow2 itself (no full-size flow)
                 return None
             return torch.nn.functional.interpolate(self.eng.flow_out * self.eng.flow_scale, scale_factor=4, mode="bilinear",

@@ -1004,6 +1004,33 @@ int ufr_sweep_metrics(const float* pred, const float* gt, const float* mask_p, c
                       int H, int W, int Hg, int Wg, int ph, int pw, int valid_in_patch, double* ws, long ws_elems, float* out,
                       int row0, int rows, ufr_stream_t stream);
 
+/* ---- feature-map statistics (csrc/feature_stats.hip) -------------------------------------------------------------------------
+ * patch_attacks/test_patch_embeddings.py takes np.mean over the pixels of every feature map of a forward; here the maps stay where
+ * the engine left them and only their per-image, per-channel SUMS leave the device, all segments of a forward in one result matrix.
+ * A segment is a chunk range of a planes buffer (kind 0: bf16 [3][chunks][images * pixels][32], value = p0 + p1 + p2 exactly) or
+ * an NCHW float32 tensor [images][channels][pixels] (kind 1; chunk0 is then the first channel and plane_stride the element
+ * count of the tensor).  For b < B, c < channels:
+ *     out[b * out_stride + out_col + c] = sum over the `pixels` pixels of image image0 + b of f(x),
+ *     f(x) = x, or, when unleaky != 0 and x < 0, the float32 y in front of a LeakyReLU of slope s = (float)unleaky with
+ *     fl(y * s) == x: among the five floats around fl(x / s), the one of smallest magnitude that satisfies it (fl(x / s) when none
+ *     does) -- the values FlowNetCHeadEngine.capture returns for `corr`, whose LeakyReLU the engine's planes hold,
+ * in float64.  Lanes >= channels of the last chunk are neither read into a sum nor written.  Two stages: every (image, chunk,
+ * pixel slab) is one workgroup that leaves 32 partial sums in `ws`, a second launch adds a channel's slabs in ascending order.  The
+ * slab count is min(128, ceil(pixels / 2048)), a function of the shape alone: no float atomics, two runs are bit-identical on
+ * every device.  The table reaches the kernels by value (UFR_FEATURE_STATS_MAX_SEGS segments per call).
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: null pointers, nseg outside 1 .. UFR_FEATURE_STATS_MAX_SEGS, a kind
+ * other than 0 / 1, non-positive sizes, images image0 .. image0 + B - 1 or chunks (channels) that leave the buffer (a planes
+ * operand holds plane_stride / (images * pixels * 32) chunks per plane), a planes pointer that is not 16-byte aligned, a negative
+ * or non-finite unleaky, B > out_rows, out_stride < out_cols, columns out_col .. out_col + channels - 1 outside out_cols, a workspace
+ * that is too small. */
+#define UFR_FEATURE_STATS_MAX_SEGS 32
+typedef struct {
+  const void* src; long plane_stride; long pixels; int kind, images, image0, B, chunk0, channels; double unleaky; long out_col;
+} ufr_feature_stats_seg;
+long ufr_feature_stats_workspace_doubles(const ufr_feature_stats_seg* segs, int nseg);   /* -1 for a table ufr_feature_stats refuses */
+int ufr_feature_stats(const ufr_feature_stats_seg* segs, int nseg, double* ws, long ws_elems, double* out, int out_rows, long out_cols,
+                      long out_stride, ufr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

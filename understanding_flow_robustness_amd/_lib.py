@@ -119,6 +119,14 @@ class AdamwHyper(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias1", "bias2")]
 
 
+class FeatureStatsSeg(C.Structure):
+    """ufr_feature_stats_seg (include/ufr_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("plane_stride", C.c_long), ("pixels", C.c_long), ("kind", C.c_int), ("images", C.c_int),
+                ("image0", C.c_int), ("B", C.c_int), ("chunk0", C.c_int), ("channels", C.c_int), ("unleaky", C.c_double),
+                ("out_col", C.c_long)]
+
+
+UFR_FEATURE_STATS_MAX_SEGS = 32
 UFR_MAX_CONE_LAYERS = 8
 UFR_PF_REGION_BAND, UFR_PF_REGION_WINDOW = 1, 2      # region kinds of ufr_flow_head_planes_backward_regions
 
@@ -273,6 +281,7 @@ SIGNATURES = {
     "ufr_adamw_step": [C.POINTER(AdamwSeg), _i, C.POINTER(AdamwHyper), _vp, _vp],
     "ufr_sweep_paste": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, C.POINTER(ConeChain), _i, _i, _vp, _vp, _vp],
     "ufr_sweep_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
+    "ufr_feature_stats": [C.POINTER(FeatureStatsSeg), _i, _vp, _l, _vp, _i, _l, _l, _vp],
 }
 PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_device_count": (C.c_int, []), "ufr_build_manifest": (C.c_char_p, []),
@@ -284,7 +293,8 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_altcorr_pyramid_workspace_bytes": (C.c_long, [_i, _i, _i, _i, _i, _i]),
          "ufr_train_loss_workspace_doubles": (C.c_long, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i]),
-         "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i])}
+         "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i]),
+         "ufr_feature_stats_workspace_doubles": (C.c_long, [C.POINTER(FeatureStatsSeg), _i])}
 
 
 def lib():

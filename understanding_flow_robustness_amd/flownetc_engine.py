@@ -878,6 +878,125 @@ class FlowNetCHeadEngine:
                     "correlation backward")
         self.g_c3a.add_(self.g_c3a_redir)
 
+    # ------------------------------------------------------------------------------------------------ analysis
+    # Feature-map capture and replacement (feature_maps.py; models/utils_model.py:160-626, models/FlowNetC.py:121-155 of the
+    # reference).  After a forward every map the analysis scripts read sits in a plane buffer; a replaced map is a chunk range
+    # the next forward does not recompute.
+    REPLACEABLE = ("conv3a", "conv3b", "corr", "conv_redir", "conv3_1")          # what FlowNetC.py:121-155 reads
+    _HEAD_SEGMENTS = {                               # key: (buffer attribute, first chunk, channels)
+        "conv_redir": ("in31", 0, 32), "corr": ("in31", 1, 441), "conv3_1": ("cat3", 0, 256), "deconv3": ("cat3", 8, 128),
+        "upsampled_flow4_to_3": ("cat3", 12, 2), "conv4": ("c4a", 0, 512), "conv4_1": ("cat4", 0, 512), "deconv4": ("cat4", 16, 256),
+        "upsampled_flow5_to_4": ("cat4", 24, 2), "conv5": ("c5a", 0, 512), "conv5_1": ("cat5", 0, 512), "deconv5": ("cat5", 16, 512),
+        "upsampled_flow6_to_5": ("cat5", 32, 2), "conv6": ("c6a", 0, 1024), "conv6_1": ("c6", 0, 1024), "deconv2": ("cat2", 4, 64),
+        "upsampled_flow3_to_2": ("cat2", 6, 2)}
+    _FLOW_KEYS = {"flow6": 6, "flow5": 5, "flow4": 4, "flow3": 3, "predict": 2}
+
+    def segment_map(self, stem=None) -> dict:
+        """{reference key: (Planes | NCHW float32 tensor, first chunk (channel), channels, first image, post-processing)} of where
+        each of the 28 maps of models/utils_model.py:283-316 sits after a forward.  `stem` = the prefix's PlaneGraph
+        (plane_graph.stem_graph over the 2B stacked frames: its c1 / c2 / c3 buffers hold conv1-3 of the first frames in images
+        0 .. B-1 and of the second frames in B .. 2B-1); without it the six stem keys are left out.  Post-processing: "unleaky"
+        for `corr` (in31 holds LeakyReLU(corr); the reference records the volume in front of the activation), else None."""
+        if not self.siamese:
+            raise RuntimeError("feature-map segments: the FlowNetC head (the FlowNetS trunk has no correlation)")
+        seg = {}
+        if stem is not None:
+            for lvl, cn in ((1, 64), (2, 128), (3, 256)):
+                p = stem.bufs[f"c{lvl}"].planes
+                seg[f"conv{lvl}a"], seg[f"conv{lvl}b"] = (p, 0, cn, 0, None), (p, 0, cn, self.B, None)
+        for key, (buf, c0, cn) in self._HEAD_SEGMENTS.items():
+            seg[key] = (getattr(self, buf), c0, cn, 0, "unleaky" if key == "corr" else None)
+        for key, k in self._FLOW_KEYS.items():
+            seg[key] = (self.flow[k], 0, 2, 0, None)
+        return seg
+
+    def capture(self, keys=None, stem=None) -> dict:
+        """{key: NCHW float32 [B,C,h,w]} of the last forward's maps, copies (`Planes.to_nchw`: p0 + p1 + p2, exact).
+        `corr` is un-leakied from conv3_1's input planes, not recomputed by the float32 correlation operator: a negative entry x
+        becomes a float32 y next to x / 0.1 with fl(y * 0.1) == x (`_unleaky`; x is such a product, so one exists within an ulp),
+        which `Planes.load_nchw(slope=LEAKY)` maps back to the same planes bit for bit."""
+        seg = self.segment_map(stem)
+        out = {}
+        for key in (list(seg) if keys is None else keys):
+            if key not in seg:
+                raise KeyError(f"capture: {key!r} is not a feature map of this forward ({', '.join(seg)})")
+            src, c0, cn, img0, post = seg[key]
+            if isinstance(src, ig.Planes):
+                t = src.to_nchw(cn, c0)[img0:img0 + self.B]
+                out[key] = _unleaky(t, ig.LEAKY) if post == "unleaky" else (t if t.shape[0] == src.B else t.clone())
+            else:
+                out[key] = src[:, c0:c0 + cn].clone()
+        return out
+
+    def forward_replaced(self, c2a, c3a, c3b, overwrite=None, keep=(), computed=None) -> torch.Tensor:
+        """`forward` (full frame, no band) with feature maps replaced, models/FlowNetC.py:121-155: `overwrite` = {key: NCHW
+        float32 [B,C,h,w]} is loaded into the key's chunks (conv3a / conv3b only as a pair, in front of the correlation and
+        conv_redir; corr in front of the LeakyReLU; conv_redir; conv3_1) and `keep` names keys whose chunks still hold a DONOR
+        forward's values on this engine: they are left as they are (the zero-copy form).  The launch that would have produced a
+        replaced segment is skipped -- unless `computed` (a dict) is given: it then runs first and its result is stored there,
+        because the reference hands back the computed map even where it overwrites it.  Keys outside REPLACEABLE are ignored, as
+        the reference ignores them.  -> flow2 (the static buffer)."""
+        if not self.siamese:
+            raise RuntimeError("feature-map replacement: the FlowNetC head")
+        ow = {k: v for k, v in (overwrite or {}).items() if k in self.REPLACEABLE}
+        keep = {k for k in keep if k in self.REPLACEABLE and k not in ow}
+        pair = lambda d: "conv3a" in d and "conv3b" in d
+        for t, name in ((c2a, "c2a"), (c3a, "c3a"), (c3b, "c3b")):
+            L.require_hip(t, name)
+        self.generation = getattr(self, "generation", 0) + 1          # a pending autograd backward of this engine is stale now
+        self._c3a, self._c3b = c3a, c3b
+        self.cat2.load_nchw(c2a, 0)
+        if pair(ow):
+            self.c3a_p.load_nchw(ow["conv3a"].contiguous(), 0)
+            self.c3b_p.load_nchw(ow["conv3b"].contiguous(), 0)
+        elif not pair(keep):
+            self.c3a_p.load_nchw(c3a, 0)
+            self.c3b_p.load_nchw(c3b, 0)
+
+        def stage(key, launch, load):
+            if key not in ow and key not in keep:
+                launch()
+                return
+            if computed is not None:
+                held = self.capture([key]) if key in keep else None          # the donor's chunks survive the computed pass
+                launch()
+                computed[key] = self.capture([key])[key]
+                if held is not None:
+                    load(held[key])
+            if key in ow:
+                load(ow[key].contiguous())
+
+        corr = lambda: L.check(L.lib().ufr_corr_forward_planes(
+            L.ptr(self.c3a_p.t), L.ptr(self.c3b_p.t), self.c3a_p.plane_stride, L.ptr(self.in31.t), self.in31.plane_stride, 1, self.B,
+            256, *self.grid[8], 21, 2, 1.0 / 256.0, ig.LEAKY, L.stream()), "correlation forward (planes)")
+        stage("corr", corr, lambda v: self.in31.load_nchw(v, 1, slope=ig.LEAKY))
+        stage("conv_redir", self.fwd["conv_redir"], lambda v: self.in31.load_nchw(v, 0))
+        stage("conv3_1", self.fwd["conv3_1"], lambda v: self.cat3.load_nchw(v, 0))
+        for name in ("conv4", "conv4_1", "conv5", "conv5_1", "conv6", "conv6_1"):
+            self.fwd[name]()
+        self._pf_forward(6)
+        for k in (5, 4, 3, 2):
+            self._up_forward(k + 1)
+            self.fwd[f"deconv{k}"]()
+            self._pf_forward(k)
+        return self.flow[2]
+
+
+def _unleaky(x: torch.Tensor, slope: float) -> torch.Tensor:
+    """The float32 y in front of LeakyReLU(slope) of x = fl(y * slope) for x < 0: among the five floats around fl(x / slope), the
+    one of smallest magnitude whose product with `slope` rounds back to x (fl(x / slope) when none does) -- the rule of
+    csrc/feature_stats.hip `undo_leaky`, so the statistics kernel sums exactly these values."""
+    s = torch.tensor(slope, dtype=torch.float32, device=x.device)
+    y0 = x / s
+    best, found = y0.clone(), x >= 0
+    bits = y0.view(torch.int32)
+    for d in (-2, -1, 0, 1, 2):
+        cand = (bits + d).view(torch.float32)
+        ok = ~found & (cand * s == x)
+        best = torch.where(ok, cand, best)
+        found = found | ok
+    return torch.where(x < 0, best, x)
+
 
 class _EngineHead(torch.autograd.Function):
     """The engine keeps its activations in static buffers, so a forward is only differentiable until the NEXT forward of

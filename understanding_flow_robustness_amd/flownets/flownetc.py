@@ -168,7 +168,9 @@ class FlowNetC(nn.Module):
 
     def forward(self, x1, x2, overwrite_feat_maps=None):
         if overwrite_feat_maps is not None:
-            raise NotImplementedError("feature-map overwriting belongs to the analysis scripts (out of scope)")
+            # models/FlowNetC.py:121-155: the analysis path (feature_maps.py), native where its gate allows
+            from ..feature_maps import forward_overwritten
+            return forward_overwritten(self, x1, x2, overwrite_feat_maps)
         B = x1.shape[0]
         x = self.normalize_correctly(torch.cat((x1, x2), 0))
         stem = None if self.return_feat_maps else self._native_stem(x)
@@ -179,6 +181,20 @@ class FlowNetC(nn.Module):
         c2a, c3a, c3b = c2[:B], c3[:B], c3[B:]
         feats = [c1[:B], c2a, c3a, c1[B:], c2[B:], c3b] if self.return_feat_maps else None
         return self._rest(c2a, c3a, c3b, feats)
+
+    def forward_torch_maps(self, x1, x2, overwrite=None):
+        """The torch spelling with every feature map of `feature_maps.FLOWNETC_KEYS` recorded where the reference records it
+        (its clones of models/FlowNetC.py:100-136 and the module outputs its forward hooks see, models/utils_model.py:160-195):
+        always the computed value, also where `overwrite` ({key: [B,C,H,W] tensor}) then replaces it.  -> (flow, {key: tensor})."""
+        B = x1.shape[0]
+        c1, c2, c3 = self._stem_torch(self.normalize_correctly(torch.cat((x1, x2), 0)))
+        maps = {"conv1a": c1[:B], "conv1b": c1[B:], "conv2a": c2[:B], "conv2b": c2[B:], "conv3a": c3[:B], "conv3b": c3[B:]}
+        c3a, c3b = c3[:B], c3[B:]
+        ow = overwrite or {}
+        if "conv3a" in ow and "conv3b" in ow:        # FlowNetC.py:121-131: only as a pair
+            c3a, c3b = ow["conv3a"], ow["conv3b"]
+        flow = self._rest(c2[:B], c3a, c3b, None, None, maps, ow)
+        return flow, maps
 
     def engine_available(self, H, W, device) -> bool:
         """Can the attack step keep this network's cached features inside the native head (patch_attack.py's windowed
@@ -196,33 +212,46 @@ class FlowNetC(nn.Module):
         from .. import _lib as L
         return L.engine_gate(self, c2a, 64, 4)
 
-    def _rest(self, c2a, c3a, c3b, feats, band=None):
-        if self._engine_ok(c2a, feats, band):
+    def _rest(self, c2a, c3a, c3b, feats, band=None, maps=None, overwrite=None):
+        """`maps` (a dict) / `overwrite`: the analysis form of `forward_torch_maps`, always the torch spelling."""
+        if maps is None and self._engine_ok(c2a, feats, band):
             from ..flownetc_engine import engine_head
             flow2 = engine_head(self, c2a, c3a, c3b, band)
             return F.interpolate(flow2 * self.div_flow, scale_factor=4, mode="bilinear", align_corners=False)
+        ow = overwrite or {}
+
+        def rec(key, value):
+            """Record the computed map; hand on what the next layer reads (FlowNetC.py:137-155: corr, conv_redir, conv3_1)."""
+            if maps is not None:
+                maps[key] = value.detach()
+            return ow[key] if key in ow and key in ("corr", "conv_redir", "conv3_1") else value
+
         out_corr = correlate(c3a.contiguous(), c3b.contiguous(), band=band)
         if feats is not None:
             feats.append(out_corr.clone())
-        out_corr = F.leaky_relu(out_corr, 0.1)
-        in_conv3_1 = torch.cat((self._cl("conv_redir", c3a), out_corr), 1)
+        out_corr = F.leaky_relu(rec("corr", out_corr), 0.1)
+        in_conv3_1 = torch.cat((rec("conv_redir", self._cl("conv_redir", c3a)), out_corr), 1)
 
-        c3_1 = self._cl("conv3_1", in_conv3_1, band, 8)
-        c4 = self._cl("conv4_1", self._cl("conv4", c3_1, band, 8), band, 16)
-        c5 = self._cl("conv5_1", self._cl("conv5", c4, band, 16))
-        c6 = self._cl("conv6_1", self._cl("conv6", c5))
+        c3_1 = rec("conv3_1", self._cl("conv3_1", in_conv3_1, band, 8))
+        c4 = rec("conv4_1", self._cl("conv4_1", rec("conv4", self._cl("conv4", c3_1, band, 8)), band, 16))
+        c5 = rec("conv5_1", self._cl("conv5_1", rec("conv5", self._cl("conv5", c4, band, 16))))
+        c6 = rec("conv6_1", self._cl("conv6_1", rec("conv6", self._cl("conv6", c5))))
 
-        flow6 = flow_head(c6, self.predict_flow6)
-        cat5 = torch.cat((c5, self._cl("deconv5", c6), flow_upsample(flow6, self.upsampled_flow6_to_5)), 1)
-        flow5 = flow_head(cat5, self.predict_flow5)
-        cat4 = torch.cat((c4, self._cl("deconv4", cat5), flow_upsample(flow5, self.upsampled_flow5_to_4)), 1)
-        flow4 = flow_head(cat4, self.predict_flow4)
-        cat3 = torch.cat((c3_1, self._cl("deconv3", cat4), flow_upsample(flow4, self.upsampled_flow4_to_3)), 1)
-        flow3 = flow_head(cat3, self.predict_flow3)
-        cat2 = torch.cat((c2a, self._cl("deconv2", cat3), flow_upsample(flow3, self.upsampled_flow3_to_2)), 1)
-        flow2 = flow_head(cat2, self.predict_flow2)
+        up = lambda k, f: rec(f"upsampled_flow{k}_to_{k - 1}", flow_upsample(f, getattr(self, f"upsampled_flow{k}_to_{k - 1}")))
+        dec = lambda k, x: rec(f"deconv{k}", self._cl(f"deconv{k}", x))
+        flow6 = rec("flow6", flow_head(c6, self.predict_flow6))
+        cat5 = torch.cat((c5, dec(5, c6), up(6, flow6)), 1)
+        flow5 = rec("flow5", flow_head(cat5, self.predict_flow5))
+        cat4 = torch.cat((c4, dec(4, cat5), up(5, flow5)), 1)
+        flow4 = rec("flow4", flow_head(cat4, self.predict_flow4))
+        cat3 = torch.cat((c3_1, dec(3, cat4), up(4, flow4)), 1)
+        flow3 = rec("flow3", flow_head(cat3, self.predict_flow3))
+        cat2 = torch.cat((c2a, dec(2, cat3), up(3, flow3)), 1)
+        flow2 = rec("predict", flow_head(cat2, self.predict_flow2))
 
-        up = lambda f: F.interpolate(f * self.div_flow, scale_factor=4, mode="bilinear", align_corners=False)
+        full = lambda f: F.interpolate(f * self.div_flow, scale_factor=4, mode="bilinear", align_corners=False)
+        if maps is not None:
+            return full(flow2)
         if self.training:
-            return tuple(up(f) for f in (flow2, flow3, flow4, flow5, flow6))
-        return (up(flow2), feats) if self.return_feat_maps else up(flow2)
+            return tuple(full(f) for f in (flow2, flow3, flow4, flow5, flow6))
+        return (full(flow2), feats) if self.return_feat_maps else full(flow2)

@@ -1,7 +1,8 @@
 """Registry level of the drop-in boundary: `get_flownet_choices`, `fetch_model`, `predict_flow`
 with the reference's names, argument meaning and string matching (models/utils_model.py:10-157,
-:627-681).  Feature-map plumbing (return_feat_maps / overwrite_feat_maps, :160-626) belongs to the
-paper's analysis scripts and is out of the hot path's scope.
+:627-681).  The feature-map plumbing of the paper's analysis scripts (return_feat_maps / overwrite_feat_maps,
+`get_feature_map_keys`, `compute_feature_map`, :160-626) is served for FlowNetC and the Robust FlowNetC family by
+feature_maps.py: on the native engines the maps are read where a forward left them.
 """
 from __future__ import annotations
 
@@ -10,6 +11,7 @@ import re
 
 import torch
 
+from ..feature_maps import compute_feature_map, get_feature_map_keys  # noqa: F401  (the reference's names, :282-316, :439-442)
 from .flownetc import FlowNetC
 from .weights import synthetic_state_dict
 
@@ -114,9 +116,21 @@ def fetch_model(args, pretrained_path: str = "pretrained_models", return_feat_ma
 
 def predict_flow(flow_net, ref_past_img, tgt_img, ref_future_img, args, return_feat_maps=False,
                  overwrite_feat_maps=None, feat_maps_to_numpy: bool = True):
-    """utils_model.py:627-681: uniform call -- RAFT takes [0,255] images and returns (low, up)."""
-    if return_feat_maps or overwrite_feat_maps:
-        raise NotImplementedError("feature-map capture/overwrite is analysis-only (out of scope)")
+    """utils_model.py:627-681: uniform call -- RAFT takes [0,255] images and returns (low, up).
+    `return_feat_maps`: (flow, {key: map}) over `get_feature_map_keys(args)` -- numpy [C,H,W] of sample 0, or with
+    `feat_maps_to_numpy=False` device tensors [B,C,H,W] -- always the computed maps, also of what `overwrite_feat_maps`
+    ({key: numpy [C,H,W] as in the reference, or a tensor [B,C,H,W]}; FlowNetC only, keys the model does not read are ignored)
+    replaces.  It does not matter whether the network was built with return_feat_maps=True.  Like the reference, an
+    `overwrite_feat_maps` without `return_feat_maps` is not looked at."""
+    if return_feat_maps:
+        from .. import feature_maps as fm
+        if not fm.served(args) or not isinstance(flow_net, FlowNetC):
+            raise NotImplementedError(f"predict_flow(return_feat_maps=True) for {args.flownet!r}: feature-map capture and "
+                                      f"replacement serve {fm.SERVED}")
+        flow, maps = fm.forward_with_maps(flow_net, tgt_img, ref_future_img, overwrite_feat_maps or None)
+        if feat_maps_to_numpy:
+            maps = {k: v[0].detach().cpu().numpy() for k, v in maps.items()}
+        return flow, maps
     if "RAFT" in args.flownet:
         _, flow_pred = flow_net(image1=tgt_img * 255.0, image2=ref_future_img * 255.0, test_mode=True)
         return flow_pred

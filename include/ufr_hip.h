@@ -1031,6 +1031,47 @@ long ufr_feature_stats_workspace_doubles(const ufr_feature_stats_seg* segs, int 
 int ufr_feature_stats(const ufr_feature_stats_seg* segs, int nseg, double* ws, long ws_elems, double* out, int out_rows, long out_cols,
                       long out_stride, ufr_stream_t stream);
 
+/* ---- MI-FGSM and input diversity on the captured step (csrc/perturb_step.hip) -------------------------------------------------
+ * global_attacks/perturb_model.py:621-757 (momentum) and :759-821 (input diversity).  Plain stores, no float atomics, every
+ * reduction in an order that the shape alone fixes: two runs are bit-identical.
+ *
+ * ufr_abs_sums: out[0] = sum |g0|, out[1] = sum |g1| over n elements each (the whole tensor, batch included, :673-678).  Stage 1
+ *   leaves min(2048, ceil(n / 1024)) pairs of float64 partials in `ws`, stage 2 (one wave) adds them in ascending order and rounds
+ *   to float32.  ufr_abs_sums_workspace_doubles(n) is the size of `ws` (-1 when n < 1).
+ * ufr_momentum_update: both frames, i < B * CHW, s0 = sums[0], s1 = sums[1] (device, as ufr_abs_sums left them):
+ *       m = fl(fl(mu * m) + fl(fl(one_minus_mu * g) / s))                  every operation rounded on its own, like torch
+ *       adv = clamp(adv -/+ lr * sign(m), lo, hi); noise = clamp(adv - img, +-eps); adv = img + noise; delta[b, frame] = noise
+ *   `frames` (bit 0 = frame 0, bit 1 = frame 1) masks the step, never the momentum (:681-691); ascent as ufr_universal_update.
+ *   s == 0 is not guarded: m becomes NaN (or inf) as in the reference.
+ * Input diversity.  `table` is a DEVICE int32 [rows][UFR_DIVERSE_COLS] of (apply, nh, nw, top, left, 0, 0, 0) and `step` a device
+ *   int32 that selects the row, so one captured launch sees a new row at each replay.  apply == 0, *step outside [0, rows) or a
+ *   row that leaves the frame copies the inputs through.  ufr_diverse_table_check validates a HOST table before it is uploaded.
+ * ufr_diverse_forward: x0, x1 = the frames resized (torch's bilinear, align_corners False, no antialias) to nh x nw, placed at
+ *   (top, left), zero elsewhere; gt_out = gt resized by torch's "nearest", placed alike, EVERY channel times (float)(nw / W) --
+ *   the validity channel too, the reference's quirk (:815).  Source indices are torch's area_pixel_compute_source_index and
+ *   nearest_neighbor_compute_source_index in float32.  With Cg == 3 *scale_t = 1 / (sum gt_out[:, 2] + 1e-8) (:141-143) from
+ *   float64 partials (ufr_diverse_workspace_doubles of them) added in a fixed order by a second one-wave launch.
+ * ufr_diverse_backward: g0, g1 = the adjoint of the frames' map applied to gx0, gx1.  Every source pixel gathers from the
+ *   destination pixels whose 2 x 2 footprint holds it (destination rows / columns within 2 of its own image, nh <= H).
+ * ufr_step_advance: *step += 1 with an ordinary store (one thread), the last launch of a step.
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: null pointers, non-positive sizes, Cg outside {2, 3}, frames outside
+ *   1..3, rows < 1, a workspace that is too small; by the table check a row with apply != 0 and nh outside 1..H, nw outside 1..W,
+ *   top < 0, left < 0, top + nh > H or left + nw > W. */
+#define UFR_DIVERSE_COLS 8
+long ufr_abs_sums_workspace_doubles(long n);
+int ufr_abs_sums(const float* g0, const float* g1, long n, double* ws, long ws_elems, float* out, ufr_stream_t stream);
+int ufr_momentum_update(const float* img0, const float* img1, const float* g0, const float* g1, const float* sums, float* m0,
+                        float* m1, float* adv0, float* adv1, float* delta, int B, int CHW, float mu, float one_minus_mu, float lr,
+                        float eps, float lo, float hi, int frames, int ascent, ufr_stream_t stream);
+int ufr_diverse_table_check(const int* table_host, int rows, int H, int W);
+long ufr_diverse_workspace_doubles(int B, int H, int W, int Cg);   /* -1 for a shape ufr_diverse_forward refuses */
+int ufr_diverse_forward(const float* adv0, const float* adv1, const float* gt, float* x0, float* x1, float* gt_out, int B, int H,
+                        int W, int Cg, const int* table, int rows, const int* step, float* scale_t, double* ws, long ws_elems,
+                        ufr_stream_t stream);
+int ufr_diverse_backward(const float* gx0, const float* gx1, float* g0, float* g1, int B, int H, int W, const int* table, int rows,
+                         const int* step, ufr_stream_t stream);
+int ufr_step_advance(int* step, ufr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

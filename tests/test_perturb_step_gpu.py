@@ -1,0 +1,331 @@
+"""GPU suite: csrc/perturb_step.hip -- MI-FGSM's momentum and the input-diversity transform on the captured attack step
+(global_attacks/perturb_model.py:621-821) -- kernel by kernel against torch on the device, then `PerturbationsModel` end to end
+on FlowNetC: fused against the step-by-step spelling (`fused=False`) and against the reference's own outputs.
+
+Bounds.  Frames in [0, 1]: a contracted and an uncontracted source index `scale * (dst + 0.5) - 0.5` differ by one rounding of a
+value below max(H, W), the interpolation weight moves by at most that, so the bilinear outputs agree within
+4 * 2^-23 * max(H, W).  The adjoint adds at most nine such weights (3 x 3 destination pixels reach a source pixel at scales in
+[1, 1/0.9]) times max|g|.  Sums are float64 partials rounded once: 1e-6 relative leaves an order of magnitude.  The momentum step
+restates torch operation by operation, so it is compared with `torch.equal`."""
+import random
+from argparse import Namespace
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import load_golden, t
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROWS = [(0, 0, 0, 0, 0), (1, 20, 30, 0, 0), (1, 18, 27, 2, 3), (1, 18, 27, 0, 0), (1, 19, 30, 1, 0)]
+SMALL_ROWS = [(1, 9, 9, 1, 0)]
+
+
+def _L():
+    from understanding_flow_robustness_amd import _lib as L
+    return L, L.lib()
+
+
+def _table(rows, H, W):
+    tab = torch.zeros(len(rows), 8, dtype=torch.int32)
+    for r, row in zip(tab, rows):
+        r[:5] = torch.tensor(row, dtype=torch.int32)
+    L, lib = _L()
+    L.check(lib.ufr_diverse_table_check(tab.data_ptr(), len(rows), H, W), "diverse table")
+    return tab.to(DEV)
+
+
+def _frame_bound(H, W):
+    return 4 * 2.0 ** -23 * max(H, W)
+
+
+def _inputs(B, H, W, Cg, seed=5):
+    g = torch.Generator().manual_seed(seed)
+    a0, a1 = torch.rand(B, 3, H, W, generator=g).to(DEV), torch.rand(B, 3, H, W, generator=g).to(DEV)
+    gt = 3 * torch.randn(B, Cg, H, W, generator=g)
+    if Cg == 3:
+        gt[:, 2] = (torch.rand(B, H, W, generator=g) > 0.3).float()
+    return a0, a1, gt.to(DEV)
+
+
+def _torch_diverse(x, row, mode, H, W):
+    ap, nh, nw, top, left = row
+    if not ap:
+        return x
+    return F.pad(F.interpolate(x, size=(nh, nw), mode=mode), (left, W - nw - left, top, H - nh - top), mode="constant", value=0)
+
+
+def _forward(a0, a1, gt, table, step):
+    L, lib = _L()
+    B, _, H, W = a0.shape
+    Cg = gt.shape[1]
+    x0, x1, go = torch.full_like(a0, 7.0), torch.full_like(a1, 7.0), torch.full_like(gt, 7.0)
+    scale = torch.full((1,), -1.0, device=DEV)
+    ws = torch.zeros(max(lib.ufr_diverse_workspace_doubles(B, H, W, Cg), 1), dtype=torch.float64, device=DEV)
+    L.check(lib.ufr_diverse_forward(L.ptr(a0), L.ptr(a1), L.ptr(gt), L.ptr(x0), L.ptr(x1), L.ptr(go), B, H, W, Cg, L.ptr(table),
+                                    table.shape[0], L.ptr(step), L.ptr(scale), L.ptr(ws), ws.numel(), L.stream()), "diverse forward")
+    return x0, x1, go, scale
+
+
+def _backward(g0, g1, table, step):
+    L, lib = _L()
+    B, _, H, W = g0.shape
+    o0, o1 = torch.full_like(g0, 7.0), torch.full_like(g1, 7.0)
+    L.check(lib.ufr_diverse_backward(L.ptr(g0), L.ptr(g1), L.ptr(o0), L.ptr(o1), B, H, W, L.ptr(table), table.shape[0], L.ptr(step),
+                                     L.stream()), "diverse backward")
+    return o0, o1
+
+
+def _cases():
+    out = [(2, 20, 30, ROWS, k) for k in range(len(ROWS) + 1)]           # the last index is past the table
+    return out + [(2, 10, 10, SMALL_ROWS, 0)]
+
+
+@pytest.mark.parametrize("Cg", [2, 3])
+@pytest.mark.parametrize("B,H,W,rows,k", _cases())
+def test_diverse_forward_matches_interpolate_and_pad(B, H, W, rows, k, Cg):
+    a0, a1, gt = _inputs(B, H, W, Cg)
+    step = torch.tensor([k], dtype=torch.int32, device=DEV)
+    x0, x1, go, scale = _forward(a0, a1, gt, _table(rows, H, W), step)
+    row = rows[k] if k < len(rows) else (0, 0, 0, 0, 0)
+    want_gt = _torch_diverse(gt, row, "nearest", H, W)
+    if row[0]:
+        want_gt = want_gt * (float(row[2]) / float(W))                     # every channel, the validity mask too (:815)
+    assert torch.equal(go, want_gt)
+    for got, src in ((x0, a0), (x1, a1)):
+        want = _torch_diverse(src, row, "bilinear", H, W)
+        if row[0]:
+            err = float((got - want).abs().max())
+            print(f"frames: max |kernel - torch| = {err:.3e} (bound {_frame_bound(H, W):.3e})")
+            assert err <= _frame_bound(H, W)
+        else:
+            assert torch.equal(got, src)
+    if Cg == 3:
+        want = 1.0 / (float(want_gt[:, 2].double().sum()) + 1e-8)
+        assert abs(float(scale) - want) <= 1e-6 * want
+    else:
+        assert float(scale) == -1.0                                        # no mask: the normaliser is the caller's constant
+
+
+@pytest.mark.parametrize("B,H,W,rows,k", _cases())
+def test_diverse_backward_is_the_adjoint(B, H, W, rows, k):
+    a0, a1, _ = _inputs(B, H, W, 2, seed=6)
+    g = torch.Generator().manual_seed(9)
+    y0, y1 = (torch.rand(B, 3, H, W, generator=g) + 0.5).to(DEV), (torch.randn(B, 3, H, W, generator=g)).to(DEV)
+    table, step = _table(rows, H, W), torch.tensor([k], dtype=torch.int32, device=DEV)
+    row = rows[k] if k < len(rows) else (0, 0, 0, 0, 0)
+    b0, b1 = _backward(y0, y1, table, step)
+    if not row[0]:
+        assert torch.equal(b0, y0) and torch.equal(b1, y1)
+        return
+    for got, y in ((b0, y0), (b1, y1)):                                    # float64 autograd of the torch spelling
+        x = torch.zeros(B, 3, H, W, dtype=torch.float64, device=DEV, requires_grad=True)
+        (want,) = torch.autograd.grad(_torch_diverse(x, row, "bilinear", H, W), x, y.double())
+        bound = 9 * _frame_bound(H, W) * float(y.abs().max())
+        err = float((got.double() - want).abs().max())
+        print(f"adjoint: max |kernel - autograd| = {err:.3e} (bound {bound:.3e})")
+        assert err <= bound
+    x0, _, _, _ = _forward(a0, a1, torch.zeros(B, 2, H, W, device=DEV), table, step)       # <D x, y> = <x, D^T y>
+    lhs, rhs = float((x0.double() * y0.double()).sum()), float((a0.double() * b0.double()).sum())
+    assert abs(lhs - rhs) <= 1e-5 * abs(lhs), (lhs, rhs)
+
+
+@pytest.mark.parametrize("n", [2 * 3 * 20 * 30, 3 * 1024 + 17, 2_100_001, 1])
+def test_abs_sums_fixed_order(n):
+    """3600 and 3089 are no multiple of the launch's stride (256 lanes x ceil(n / 1024) workgroups); 2 100 001 is past the size at
+    which the workgroup count stops growing."""
+    L, lib = _L()
+    g = torch.Generator().manual_seed(n)
+    g0, g1 = torch.randn(n, generator=g).to(DEV), (1e-3 * torch.randn(n, generator=g)).to(DEV)
+    ws = torch.zeros(lib.ufr_abs_sums_workspace_doubles(n), dtype=torch.float64, device=DEV)
+    outs = []
+    for _ in range(2):
+        out = torch.zeros(2, device=DEV)
+        ws.fill_(float("nan"))
+        L.check(lib.ufr_abs_sums(L.ptr(g0), L.ptr(g1), n, L.ptr(ws), ws.numel(), L.ptr(out), L.stream()), "abs sums")
+        outs.append(out)
+    assert torch.equal(outs[0], outs[1])
+    for got, src in zip(outs[0].tolist(), (g0, g1)):
+        want = float(src.double().abs().sum())
+        assert abs(got - want) <= 1e-6 * want
+
+
+def _momentum_call(img0, img1, g0, g1, m0, m1, adv0, adv1, mu, lr, eps, frames, ascent):
+    L, lib = _L()
+    B, CHW = img0.shape[0], img0[0].numel()
+    n = B * CHW
+    ws = torch.zeros(lib.ufr_abs_sums_workspace_doubles(n), dtype=torch.float64, device=DEV)
+    sums, delta = torch.zeros(2, device=DEV), torch.zeros(B, 2, *img0.shape[1:], device=DEV)
+    L.check(lib.ufr_abs_sums(L.ptr(g0), L.ptr(g1), n, L.ptr(ws), ws.numel(), L.ptr(sums), L.stream()), "abs sums")
+    L.check(lib.ufr_momentum_update(L.ptr(img0), L.ptr(img1), L.ptr(g0), L.ptr(g1), L.ptr(sums), L.ptr(m0), L.ptr(m1), L.ptr(adv0),
+                                    L.ptr(adv1), L.ptr(delta), B, CHW, mu, 1.0 - mu, lr, eps, 0.0, 1.0, frames, ascent, L.stream()),
+            "momentum update")
+    return sums, delta
+
+
+def _same(a, b):
+    """torch.equal that lets NaN equal NaN (s == 0 makes the momentum NaN on both sides)."""
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a, nan=0.0), torch.nan_to_num(b, nan=0.0))
+
+
+@pytest.mark.parametrize("zero_gradient", [False, True])
+@pytest.mark.parametrize("mode,frames", [("both", 3), ("left", 1), ("right", 2)])
+def test_momentum_update_equals_the_torch_restatement(mode, frames, zero_gradient):
+    mu, lr, eps = 0.47, 0.008, 0.02
+    B, H, W = 2, 20, 30
+    g = torch.Generator().manual_seed(17)
+    img0, img1 = torch.rand(B, 3, H, W, generator=g).to(DEV), torch.rand(B, 3, H, W, generator=g).to(DEV)
+    img0[0, 0, :2] = 0.0
+    img1[1, 2, -2:] = 1.0                                                   # the [0, 1] clamp binds somewhere
+    start = [(0.02 * (torch.rand(B, 3, H, W, generator=g) - 0.5)).to(DEV) for _ in range(2)]
+    ms = [(1e-4 * torch.randn(B, 3, H, W, generator=g)).to(DEV) for _ in range(2)]
+    gs = [(1e-3 * torch.randn(B, 3, H, W, generator=g)).to(DEV) for _ in range(2)]
+    if zero_gradient:
+        gs[1].zero_()                                                       # sum |g1| == 0: 0 / 0
+    imgs = [img0, img1]
+    advs = [torch.clamp(i + s, 0.0, 1.0) for i, s in zip(imgs, start)]
+    k_m, k_adv = [m.clone() for m in ms], [a.clone() for a in advs]
+    sums, delta = _momentum_call(img0, img1, gs[0], gs[1], k_m[0], k_m[1], k_adv[0], k_adv[1], mu, lr, eps, frames, 1)
+    assert (float(sums[1]) == 0.0) == zero_gradient
+    for f in range(2):                                                      # perturb_model.py:673-710 with the kernel's own s
+        m = mu * ms[f] + (1.0 - mu) * gs[f] / sums[f]
+        noise = lr * torch.sign(m) if frames & (1 << f) else torch.zeros_like(m)
+        adv = torch.clamp(advs[f] + noise, 0.0, 1.0)
+        noise = torch.clamp(adv - imgs[f], -eps, eps)
+        assert _same(k_m[f], m), f"momentum of frame {f}"
+        assert torch.equal(k_adv[f], imgs[f] + noise), f"adversarial frame {f}"
+        assert torch.equal(delta[:, f], noise), f"delta of frame {f}"
+        assert bool(torch.isnan(k_m[f]).all()) == (zero_gradient and f == 1)
+        assert not torch.isnan(k_adv[f]).any()
+
+
+def test_step_index_selects_a_new_row_at_each_graph_replay():
+    L, lib = _L()
+    B, H, W = 2, 20, 30
+    rows = [ROWS[2], ROWS[4]]
+    a0, a1, gt = _inputs(B, H, W, 3)
+    table, step = _table(rows, H, W), torch.zeros(1, dtype=torch.int32, device=DEV)
+    x0, x1, go = torch.zeros_like(a0), torch.zeros_like(a1), torch.zeros_like(gt)
+    scale = torch.zeros(1, device=DEV)
+    ws = torch.zeros(lib.ufr_diverse_workspace_doubles(B, H, W, 3), dtype=torch.float64, device=DEV)
+
+    def launches():
+        L.check(lib.ufr_diverse_forward(L.ptr(a0), L.ptr(a1), L.ptr(gt), L.ptr(x0), L.ptr(x1), L.ptr(go), B, H, W, 3, L.ptr(table), 2,
+                                        L.ptr(step), L.ptr(scale), L.ptr(ws), ws.numel(), L.stream()), "diverse forward")
+        L.check(lib.ufr_step_advance(L.ptr(step), L.stream()), "step advance")
+
+    side = torch.cuda.Stream(device=DEV)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        launches()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    assert int(step) == 1
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        launches()
+    step.zero_()
+    for k, row in enumerate(rows + [(0, 0, 0, 0, 0)]):                      # the third replay is past the table: a copy
+        graph.replay()
+        torch.cuda.synchronize()
+        assert int(step) == k + 1
+        want = _torch_diverse(a0, row, "bilinear", H, W)
+        assert float((x0 - want).abs().max()) <= _frame_bound(H, W)
+        want_gt = _torch_diverse(gt, row, "nearest", H, W) * (float(row[2]) / float(W)) if row[0] else gt
+        assert torch.equal(go, want_gt)
+        assert abs(float(scale) * (float(want_gt[:, 2].double().sum()) + 1e-8) - 1.0) <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------------------------------ end to end
+EPS = 0.02
+CONFIGS = {"ifgsm_di": ("ifgsm", 1.0, 2), "mifgsm_di": ("mifgsm", 1.0, 2), "mifgsm_di_valid": ("mifgsm", 0.5, 3)}
+
+
+def _accept(got, want, what):
+    """The condition of test_perturbations_model_matches_reference: the outputs are step multiples of a sign, and a gradient
+    within rounding of zero may flip on another platform; everything else agrees to float rounding."""
+    diff = (got.cpu() - want.cpu()).abs()
+    frac = float((diff > 1e-6).float().mean())
+    print(f"{what}: {frac:.2e} of the pixels differ, max {float(diff.max()):.3e}")
+    assert frac < 5e-3, f"{what}: {frac:.2e} of the pixels differ"
+    assert float(diff.max()) <= 2 * EPS + 1e-6
+
+
+@pytest.fixture(scope="module")
+def setup():
+    from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
+    z, base = load_golden("perturb_model_di_flownetc"), load_golden("perturb_model_flownetc")
+    args = Namespace(flownet="FlowNetC", flow_loss="l2")
+    net = fetch_model(args, synthetic_seed=0).to(DEV)
+    i0, i1, gt2 = t(base["img0"], DEV), t(base["img1"], DEV), t(base["gt"], DEV)
+    gt3 = torch.cat((gt2, t(z["valid"], DEV).float()), 1)
+    return dict(z=z, args=args, net=net, i0=i0, i1=i1, gt={2: gt2, 3: gt3}, runs={})
+
+
+def _run(s, method, p, i0, i1, gt, seed, fused):
+    from understanding_flow_robustness_amd.perturb_model import PerturbationsModel
+    pm = PerturbationsModel(perturb_method=method, perturb_mode="both", output_norm=EPS, n_step=3, learning_rate=0.008,
+                            momentum=0.47, probability_diverse_input=p, disparity=False, args=s["args"], fused=fused)
+    torch.manual_seed(seed)
+    random.seed(seed)
+    n0, n1, _, _ = pm.forward(s["net"], i0, i1, gt)
+    return n0, n1, float(torch.rand(1)), random.random()
+
+
+def _both(s, tag):
+    """(fused, eager) of one golden configuration, computed once; fused first, which freezes the parameters like every attack."""
+    if tag not in s["runs"]:
+        method, p, cg = CONFIGS[tag]
+        seed = int(s["z"][f"{tag}_seed"])
+        s["runs"][tag] = tuple(_run(s, method, p, s["i0"], s["i1"], s["gt"][cg], seed, fused) for fused in (True, False))
+    return s["runs"][tag]
+
+
+@pytest.mark.parametrize("tag", list(CONFIGS))
+def test_fused_matches_the_eager_spelling_and_the_reference(setup, tag):
+    fused, eager = _both(setup, tag)
+    z = setup["z"]
+    for k in range(2):
+        _accept(fused[k], eager[k], f"{tag} noise{k}, fused against eager")
+        _accept(fused[k], t(z[f"{tag}_noise{k}"]), f"{tag} noise{k}, fused against the reference")
+    assert float(fused[0].abs().max()) > 0.5 * EPS                         # an attack happened
+
+
+@pytest.mark.parametrize("tag", list(CONFIGS))
+def test_generators_end_where_the_eager_call_and_the_reference_leave_them(setup, tag):
+    fused, eager = _both(setup, tag)
+    z = setup["z"]
+    assert fused[2:] == eager[2:]
+    assert fused[2] == float(z[f"{tag}_next_rand"][0]) and fused[3] == float(z[f"{tag}_next_random"])
+
+
+def test_fused_matches_eager_on_a_batch_of_two(setup):
+    s = setup
+    i0, i1 = torch.cat((s["i0"], s["i1"])), torch.cat((s["i1"], s["i0"]))
+    gt = torch.cat((s["gt"][3], s["gt"][3].flip(-1)))
+    fused, eager = (_run(s, "mifgsm", 0.5, i0, i1, gt, 13, f) for f in (True, False))
+    for k in range(2):
+        _accept(fused[k], eager[k], f"B = 2, noise{k}")
+    assert fused[2:] == eager[2:]
+
+
+def test_mifgsm_runs_on_one_cached_captured_step():
+    """The evidence that MI-FGSM left the step-by-step path: one captured step on the network, reused by a second model."""
+    from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
+    from understanding_flow_robustness_amd.perturb_model import PerturbationsModel
+    base = load_golden("perturb_model_flownetc")
+    args = Namespace(flownet="FlowNetC", flow_loss="l2")
+    net = fetch_model(args, synthetic_seed=0).to(DEV)
+    i0, i1, gt = t(base["img0"], DEV), t(base["img1"], DEV), t(base["gt"], DEV)
+    kw = dict(perturb_method="mifgsm", perturb_mode="both", output_norm=EPS, n_step=3, learning_rate=0.008, momentum=0.47,
+              probability_diverse_input=0.0, disparity=False, args=args)
+    first = PerturbationsModel(**kw).forward(net, i0, i1, gt)
+    steps = net.__dict__["_ufr_perturb_steps"]
+    assert len(steps) == 1
+    (step,) = steps.values()
+    assert step.graph is not None and step.mu == pytest.approx(0.47) and not step.diverse
+    second = PerturbationsModel(**kw).forward(net, i0, i1, gt)
+    assert len(steps) == 1 and next(iter(steps.values())) is step
+    assert torch.equal(first[0], second[0]) and torch.equal(first[1], second[1])       # load() restarts the momentum
+    _accept(first[0], t(base["mifgsm_noise0"]), "mifgsm noise0 against the reference")

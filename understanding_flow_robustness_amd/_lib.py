@@ -282,7 +282,14 @@ SIGNATURES = {
     "ufr_sweep_paste": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, C.POINTER(ConeChain), _i, _i, _vp, _vp, _vp],
     "ufr_sweep_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
     "ufr_feature_stats": [C.POINTER(FeatureStatsSeg), _i, _vp, _l, _vp, _i, _l, _l, _vp],
+    "ufr_abs_sums": [_vp, _vp, _l, _vp, _l, _vp, _vp],
+    "ufr_momentum_update": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _vp],
+    "ufr_diverse_table_check": [_vp, _i, _i, _i],
+    "ufr_diverse_forward": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _l, _vp],
+    "ufr_diverse_backward": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp],
+    "ufr_step_advance": [_vp, _vp],
 }
+DIVERSE_COLS = 8         # UFR_DIVERSE_COLS (include/ufr_hip.h)
 PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_device_count": (C.c_int, []), "ufr_build_manifest": (C.c_char_p, []),
          "ufr_igemm_variant_fallbacks": (C.c_int, []),
@@ -294,7 +301,9 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_train_loss_workspace_doubles": (C.c_long, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i]),
          "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i]),
-         "ufr_feature_stats_workspace_doubles": (C.c_long, [C.POINTER(FeatureStatsSeg), _i])}
+         "ufr_feature_stats_workspace_doubles": (C.c_long, [C.POINTER(FeatureStatsSeg), _i]),
+         "ufr_abs_sums_workspace_doubles": (C.c_long, [_l]),
+         "ufr_diverse_workspace_doubles": (C.c_long, [_i, _i, _i, _i])}
 
 
 def lib():

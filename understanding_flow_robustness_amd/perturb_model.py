@@ -1,12 +1,19 @@
 """Per-image global attacks of global_attacks/perturb_model.py for optical flow (`disparity=False`):
 `compute_flow_loss` (:102-145) and `PerturbationsModel` with FGSM (:423-473), I-FGSM / I-FGM
-(:475-619), MI-FGSM (:621-757) and the "none" method; input diversity (:759-821) runs eagerly.
+(:475-619), MI-FGSM / MI-FGM (:621-757), input diversity (:759-821) and the "none" method.
 
-The iterative methods reuse the fused universal-perturbation step (universal_perturbation.py): the
-reference's I-FGSM is the same arithmetic with gradient ASCENT (`image + lr*sign(grad)`, :557-571),
-descent when `targeted`.  The two noise methods (uniform :332-382, gaussian :274-330) draw on the host like
-the reference and upload once; `imagecorruptions` methods are CPU image-library code and out of the hot
-path's scope.
+The iterative methods reuse the fused, graph-captured universal-perturbation step (universal_perturbation.py):
+the reference's I-FGSM is the same arithmetic with gradient ASCENT (`image + lr*sign(grad)`, :557-571),
+descent when `targeted`.  MI-FGSM's L1-normalised momentum and the input-diversity resize-and-pad with its
+adjoint are launches of the same captured step (csrc/perturb_step.hip).  The host draws the transforms of all
+`n_step` steps before the first one -- `torch.rand(1)` per step and, only when it does not exceed the
+probability, four `random.randint` -- which is the order and the amount the reference consumes, uploads them
+once, and does no work between the steps.  `fused=False` keeps the step-by-step torch spelling
+(`_iterative_eager`) as the comparison leg of the tests and of tools/bench_perturb_model.py.
+
+The two noise methods (uniform :332-382, gaussian :274-330) draw on the host like the reference and upload
+once; `imagecorruptions` methods are CPU image-library code and out of the hot path's scope (SURVEY.md 2,
+row 14).
 """
 from __future__ import annotations
 
@@ -83,7 +90,7 @@ class PerturbationsModel:
 
     def __init__(self, perturb_method="fgsm", perturb_mode="both", output_norm=0.02, n_step=40, learning_rate=2e-3,
                  momentum=0.47, probability_diverse_input=0.0, device=torch.device("cuda"), disparity=False,
-                 targeted=False, show_perturbation_evolution=None, print_out=False, args=None, use_graph=True):
+                 targeted=False, show_perturbation_evolution=None, print_out=False, args=None, use_graph=True, fused=True):
         if disparity:
             raise NotImplementedError("stereo (disparity) models are not part of this repository's flow path")
         if show_perturbation_evolution:
@@ -91,7 +98,7 @@ class PerturbationsModel:
         self.method, self.mode = perturb_method, perturb_mode
         self.eps, self.n_step, self.lr, self.mu = float(output_norm), int(n_step), float(learning_rate), float(momentum)
         self.p_diverse = float(probability_diverse_input)
-        self.targeted, self.args, self.use_graph = bool(targeted), args, use_graph
+        self.targeted, self.args, self.use_graph, self.fused = bool(targeted), args, use_graph, bool(fused)
         self._steps = {}
 
     # ------------------------------------------------------------------------------------------ helpers
@@ -133,13 +140,27 @@ class PerturbationsModel:
         g0, g1 = self._grads(model, image0, image1, ground_truth)          # :442-456
         return self._mode_mask(self.eps * torch.sign(g0), self.eps * torch.sign(g1))
 
-    def _iterative_step(self, model, image0, ground_truth):
+    def _diverse_table(self, oh, ow):
+        """The transforms of all `n_step` steps, drawn in the order `_diverse_input` draws them one step at a time: host int32
+        [n_step, 8] rows (apply, nh, nw, top, left, 0, 0, 0).  Both generators end where the reference leaves them."""
+        table = torch.zeros(self.n_step, L.DIVERSE_COLS, dtype=torch.int32)
+        for row in table:
+            if torch.rand(1) > self.p_diverse:
+                continue
+            nh, nw = random.randint(int(oh - oh / 10.0), oh), random.randint(int(ow - ow / 10.0), ow)
+            top = random.randint(0, oh - nh)
+            left = random.randint(0, ow - nw)
+            row[:5] = torch.tensor([1, nh, nw, top, left], dtype=torch.int32)
+        return table
+
+    def _iterative_step(self, model, image0, ground_truth, momentum=False):
         B, _, H, W = image0.shape
         # cached on the network (a new PerturbationsModel per training batch, train.py:172-186, must not
         # re-capture the graph): weights are read through their storage, so optimiser updates are seen
         self._steps = _engine_cache(model, "_ufr_perturb_steps")
         key = (B, H, W, ground_truth.shape[1], self.method, self.mode, self.lr, self.eps, self.targeted, self.use_graph,
-               getattr(self.args, "flow_loss", None), getattr(self.args, "flownet", None))
+               getattr(self.args, "flow_loss", None), getattr(self.args, "flownet", None),
+               self.mu if momentum else None, self.p_diverse > 0.0)
         step = self._steps.get(key)
         if step is None:
             sargs = Namespace(**vars(self.args))
@@ -148,16 +169,21 @@ class PerturbationsModel:
             sargs.add_gaussian = not self.targeted                        # ascent on the loss unless targeted
             step = self._steps[key] = UniversalPerturbationStep(model, sargs, B, H, W, gt_channels=ground_truth.shape[1],
                                                                 device=image0.device, shared=False,
-                                                                use_graph=self.use_graph)
+                                                                use_graph=self.use_graph,
+                                                                momentum=self.mu if momentum else None,
+                                                                diverse=self.p_diverse > 0.0)
         return step
 
-    def _ifgsm(self, model, image0, image1, ground_truth):
-        if self.p_diverse > 0.0:
-            return self._iterative_eager(model, image0, image1, ground_truth, momentum=False)
-        step = self._iterative_step(model, image0, ground_truth)
+    def _iterative(self, model, image0, image1, ground_truth, momentum):
+        """:475-619 / :621-757 on the cached captured step; the draws of `_diverse_input` happen up front (the reference draws
+        `torch.rand(1)` every step whatever the probability, so this does too)."""
+        if not self.fused:
+            return self._iterative_eager(model, image0, image1, ground_truth, momentum=momentum)
+        table = self._diverse_table(*image0.shape[2:])
+        step = self._iterative_step(model, image0, ground_truth, momentum)
         zero = torch.zeros(image0.shape[0], 2, *image0.shape[1:], device=image0.device)
         step.load(image0, image1, zero, ground_truth)
-        step.run(self.n_step)
+        step.run(self.n_step, table if step.diverse else None)
         return step.delta[:, 0].clone(), step.delta[:, 1].clone()
 
     def _iterative_eager(self, model, image0, image1, ground_truth, momentum):
@@ -210,9 +236,9 @@ class PerturbationsModel:
         if self.method in ("fgsm", "fgm"):
             noise0, noise1 = self._fgsm(model, image0, image1, ground_truth)
         elif self.method in ("ifgsm", "ifgm"):
-            noise0, noise1 = self._ifgsm(model, image0, image1, ground_truth)
+            noise0, noise1 = self._iterative(model, image0, image1, ground_truth, momentum=False)
         elif self.method in ("mifgsm", "mifgm"):
-            noise0, noise1 = self._iterative_eager(model, image0, image1, ground_truth, momentum=True)
+            noise0, noise1 = self._iterative(model, image0, image1, ground_truth, momentum=True)
         elif self.method == "gaussian":
             noise0, noise1 = self._gaussian(image0, image1)
         elif self.method == "uniform":

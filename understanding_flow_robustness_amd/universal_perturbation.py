@@ -15,6 +15,11 @@ identical update.  For B = 1 its adversarial frames equal the reference's wherev
 image-range clamp does not bind (clamping to [0,1] then to img+-eps is clamping to the
 intersection); where it binds, the reference folds the clamp into its per-sample noise while the
 shared delta stays image-independent (tests/test_models_cpu.py pins both statements).
+
+Per-sample steps take two keyword-only options for `perturb_model.PerturbationsModel` (csrc/perturb_step.hip):
+`momentum=mu` replaces ufr_universal_update by ufr_abs_sums + ufr_momentum_update (MI-FGSM, perturb_model.py:621-757),
+`diverse=True` puts ufr_diverse_forward in front of the network and ufr_diverse_backward behind its data gradient (input
+diversity, :759-821), the transform of each step read from a device table through a device-resident step index.
 """
 from __future__ import annotations
 
@@ -40,9 +45,17 @@ def add_universal_perturbation(image0, image1, universal_perturbation, lower_bou
 
 
 class UniversalPerturbationStep:
+    MAX_ROWS = 1024                     # rows of the device table of input-diversity transforms (steps of one run)
+
     def __init__(self, model, args, batch, height, width, gt_channels=2, device="cuda:0", shared=False,
-                 exchange: ShardedExchange | None = None, use_graph=True, warmup=2):
+                 exchange: ShardedExchange | None = None, use_graph=True, warmup=2, *, momentum=None, diverse=False):
+        """`momentum` = mu turns the step into MI-FGSM's (perturb_model.py:621-757: an L1-normalised running gradient, the step
+        along its sign); `diverse` puts the input-diversity transform (:759-821) in front of the network, its parameters read per
+        step from a device table that `run` uploads (csrc/perturb_step.hip).  Without them the step is what it always was."""
         L.lib()
+        if (momentum is not None or diverse) and (shared or exchange is not None):
+            raise NotImplementedError("momentum and input diversity exist for per-sample perturbations only, not for the shared "
+                                      "(multi-rank) perturbation")
         self.model, self.args = model, args
         self.B, self.H, self.W, self.Cg = batch, height, width, gt_channels
         self.dev = torch.device(device)
@@ -77,6 +90,23 @@ class UniversalPerturbationStep:
         self.loss_cur = self.packed[2 * self.CHW:]
         self.scale_t = torch.ones(1, **f32)     # 1/normaliser of the loss, device-resident
         self.loss_ws = torch.zeros(L.LOSS_PARTIALS, **f32)     # workgroup partials of the fixed-order loss reduction
+        self.mu, self.diverse = (None if momentum is None else float(momentum)), bool(diverse)
+        if self.mu is not None:
+            self.m0, self.m1 = torch.zeros_like(self.img0), torch.zeros_like(self.img0)
+            self.abs_sums = torch.zeros(2, **f32)
+            n = batch * self.CHW
+            self.abs_ws = torch.zeros(L.lib().ufr_abs_sums_workspace_doubles(n), dtype=torch.float64, device=self.dev)
+        if self.diverse:
+            self.x0 = torch.zeros_like(self.img0).requires_grad_(True)      # what the network reads: leaves written in place
+            self.x1 = torch.zeros_like(self.img0).requires_grad_(True)
+            self.gt_d = torch.zeros_like(self.gt)
+            self.gd0, self.gd1 = torch.zeros_like(self.img0), torch.zeros_like(self.img0)
+            self.table = torch.zeros(self.MAX_ROWS, L.DIVERSE_COLS, dtype=torch.int32, device=self.dev)
+            self.step_index = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            ws = L.lib().ufr_diverse_workspace_doubles(batch, height, width, gt_channels)
+            if ws < 0:
+                raise ValueError(f"input diversity: bad shape {batch} x {height} x {width}, {gt_channels} ground-truth channels")
+            self.diverse_ws = torch.zeros(max(ws, 1), dtype=torch.float64, device=self.dev)
         L.freeze_parameters(self.model)                         # patch_attack.release() restores the caller's flags
         self.model.eval()
         self.graph = self.graph_b = None
@@ -89,16 +119,43 @@ class UniversalPerturbationStep:
             L.ptr(self.delta), self.B, self.CHW, self.lr, self.eps, 0.0, 1.0, self.use_sign, self.frames,
             self.ascent, int(self.shared), mode, L.stream()), "universal update")
 
+    def _momentum_update(self, g0, g1):
+        """:673-710: sum|g| of each frame over the whole batch, then momentum and update in one launch."""
+        lib = L.lib()
+        L.check(lib.ufr_abs_sums(L.ptr(g0), L.ptr(g1), self.B * self.CHW, L.ptr(self.abs_ws), self.abs_ws.numel(),
+                                 L.ptr(self.abs_sums), L.stream()), "abs sums")
+        L.check(lib.ufr_momentum_update(L.ptr(self.img0), L.ptr(self.img1), L.ptr(g0), L.ptr(g1), L.ptr(self.abs_sums),
+                                        L.ptr(self.m0), L.ptr(self.m1), L.ptr(self.adv0), L.ptr(self.adv1), L.ptr(self.delta),
+                                        self.B, self.CHW, self.mu, 1.0 - self.mu, self.lr, self.eps, 0.0, 1.0, self.frames,
+                                        self.ascent, L.stream()), "momentum update")
+
     def _part_a(self):
         self.loss_cur.zero_()
-        flow = predict_flow(self.model, None, self.adv0, self.adv1, self.args).contiguous()
-        L.check(L.lib().ufr_flow_loss_ex(L.ptr(flow), L.ptr(self.gt), L.ptr(self.g_flow), L.ptr(self.loss_cur), self.B,
+        in0, in1, gt = self.adv0, self.adv1, self.gt
+        if self.diverse:          # the step's row of the table: frames and ground truth resized and padded, scale_t with a mask
+            in0, in1, gt = self.x0, self.x1, self.gt_d
+            L.check(L.lib().ufr_diverse_forward(L.ptr(self.adv0), L.ptr(self.adv1), L.ptr(self.gt), L.ptr(in0), L.ptr(in1),
+                                                L.ptr(gt), self.B, self.H, self.W, self.Cg, L.ptr(self.table), self.MAX_ROWS,
+                                                L.ptr(self.step_index), L.ptr(self.scale_t), L.ptr(self.diverse_ws),
+                                                self.diverse_ws.numel(), L.stream()), "diverse forward")
+        flow = predict_flow(self.model, None, in0, in1, self.args).contiguous()
+        L.check(L.lib().ufr_flow_loss_ex(L.ptr(flow), L.ptr(gt), L.ptr(self.g_flow), L.ptr(self.loss_cur), self.B,
                                          self.H * self.W, self.Cg, self.kind, 0.0, L.ptr(self.scale_t), L.ptr(self.loss_ws),
                                          L.stream()), "flow loss")
-        g0, g1 = torch.autograd.grad(flow, (self.adv0, self.adv1), self.g_flow, allow_unused=True)
+        g0, g1 = torch.autograd.grad(flow, (in0, in1), self.g_flow, allow_unused=True)
         g0 = torch.zeros_like(self.img0) if g0 is None else g0.contiguous()
         g1 = torch.zeros_like(self.img1) if g1 is None else g1.contiguous()   # :479-483
-        self._update(g0, g1, 1 if self.world > 1 else 0)
+        if self.diverse:          # back through the resize to the adversarial frames
+            L.check(L.lib().ufr_diverse_backward(L.ptr(g0), L.ptr(g1), L.ptr(self.gd0), L.ptr(self.gd1), self.B, self.H, self.W,
+                                                 L.ptr(self.table), self.MAX_ROWS, L.ptr(self.step_index), L.stream()),
+                    "diverse backward")
+            g0, g1 = self.gd0, self.gd1
+        if self.mu is not None:
+            self._momentum_update(g0, g1)
+        else:
+            self._update(g0, g1, 1 if self.world > 1 else 0)
+        if self.diverse:
+            L.check(L.lib().ufr_step_advance(L.ptr(self.step_index), L.stream()), "step advance")
 
     def _iteration(self):
         if self.graph is not None:
@@ -151,16 +208,46 @@ class UniversalPerturbationStep:
             else:
                 per_pix = 2 if self.kind == 2 else 1
                 self.scale_t.fill_(1.0 / (self.B * self.world * self.H * self.W * per_pix))
+            if self.mu is not None:
+                self.m0.zero_(); self.m1.zero_()
+            if self.diverse:
+                self.step_index.zero_()
 
-    def run(self, n_step):
+    def _upload_table(self, n_step, table):
+        """The transforms of the next `n_step` steps: host int32 [n_step, 8] rows (apply, nh, nw, top, left, 0, 0, 0), checked on
+        the host (csrc/perturb_step.hip refuses a row that leaves the frame), uploaded once; the step index restarts at row 0."""
+        if table is None:
+            raise ValueError("a step with input diversity needs the table of its transforms: run(n_step, table)")
+        table = torch.as_tensor(table, dtype=torch.int32).contiguous()
+        if table.is_cuda or tuple(table.shape) != (int(n_step), L.DIVERSE_COLS):
+            raise ValueError(f"the table of transforms is a host tensor of exactly [{int(n_step)}, {L.DIVERSE_COLS}] for "
+                             f"{int(n_step)} steps, got {tuple(table.shape)} on {table.device}")
+        if int(n_step) > self.MAX_ROWS:
+            raise ValueError(f"{int(n_step)} steps with input diversity: the device table holds {self.MAX_ROWS} rows")
+        if int(n_step) > 0:
+            L.check(L.lib().ufr_diverse_table_check(table.data_ptr(), int(n_step), self.H, self.W), "diverse table")
+        with torch.no_grad():
+            self.table.zero_()
+            self.table[:int(n_step)].copy_(table)
+            self.step_index.zero_()
+
+    def run(self, n_step, table=None):
         with torch.cuda.device(self.dev):
+            if self.diverse:
+                self._upload_table(n_step, table)
+            elif table is not None:
+                raise ValueError("this step was built without input diversity and takes no table")
             if not self._captured:
-                saved = (self.img0.clone(), self.img1.clone(), self.delta.clone(), self.gt.clone(),
-                         self.adv0.detach().clone(), self.adv1.detach().clone())
+                state = [self.img0, self.img1, self.delta, self.gt, self.adv0, self.adv1, self.scale_t]
+                if self.mu is not None:
+                    state += [self.m0, self.m1]
+                if self.diverse:
+                    state += [self.step_index]
+                saved = [x.detach().clone() for x in state]
                 self._capture()
                 with torch.no_grad():
-                    self.img0.copy_(saved[0]); self.img1.copy_(saved[1]); self.delta.copy_(saved[2])
-                    self.gt.copy_(saved[3]); self.adv0.copy_(saved[4]); self.adv1.copy_(saved[5])
+                    for x, keep in zip(state, saved):
+                        x.copy_(keep)
             for _ in range(int(n_step)):
                 self._iteration()
 

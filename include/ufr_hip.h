@@ -692,6 +692,31 @@ typedef struct {
                                                   epilogue and leaves the counter at zero for the next launch.  NULL: the reduce kernel follows. */
 } ufr_igemm_desc;
 int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream);
+/* Re-cutting an under-filled last round (additive entries, the ABI version and the descriptor stay).  The ping-pong form (variant 6)
+ * runs one 256 x 128 tile per workgroup and one workgroup per CU, so a launch of T tiles on R resident workgroups costs ceil(T / R)
+ * rounds however few tiles the last one holds.  The plan keeps the full rounds as they are -- the first floor(T / R) * R / Nt row
+ * tiles, Nt = Npad / 128 -- and splits only the remaining row tiles (a contiguous row range at the END of the row grid) over K:
+ * S = min(R / tail_tiles, ktiles / 8, 8) slices of ceil(ktiles / S) K tiles, fp32 slabs [S][tail_rows][Npad] in `ws`, added in
+ * ascending order by the reduce kernel over the tail's rows only.  Every row of the full part is what ufr_igemm with splitk = 1
+ * computes and every row of the tail what ufr_igemm with splitk = S computes, bit for bit.
+ * ufr_igemm_tail_plan is host arithmetic (no HIP call; resident_workgroups = 0: 256, the MI355X's CU count).  `on` = 0 -- then
+ * ufr_igemm_balanced IS ufr_igemm -- when there is no full round (T < R), no under-filled one (T % R == 0), fewer than two slices,
+ * nphase != 1, Npad % 128 != 0, variant != 6, products != 6, tickets, no_reduce, a `tail` output, splitk > 1, or when the
+ * predicted K steps (a workgroup = its K tiles + ~6 for the epilogue; steps_after includes ~10 for the reduce launch) are not
+ * fewer than before.  ufr_igemm_balanced: resident_workgroups = 0 asks the current device for its CU count; a plan that is on
+ * with ws == NULL or ws_floats below the plan's is refused (UFR_EINVAL) before any launch. */
+typedef struct {
+  int on;
+  int row_tiles, col_tiles;                    /* Mt = ceil(M / 256), Nt */
+  int full_row_tiles, tail_row_tiles;          /* full + tail = Mt; the tail's first row is full_row_tiles * 256 */
+  int tail_row0, tail_rows;                    /* rows [tail_row0, tail_row0 + tail_rows) of the row grid (tail_rows ends at M) */
+  int slices, slice_ktiles, ktiles;            /* S, ceil(ktiles / S), K tiles of the launch */
+  int workgroups;                              /* full tiles + tail tiles * S */
+  long ws_floats;                              /* S * tail_rows * Npad */
+  int steps_before, steps_after;               /* predicted K steps of the critical path */
+} ufr_igemm_tail_plan_t;
+int ufr_igemm_tail_plan(const ufr_igemm_desc* d, int resident_workgroups, ufr_igemm_tail_plan_t* plan);
+int ufr_igemm_balanced(const ufr_igemm_desc* d, int resident_workgroups, float* ws, long ws_floats, ufr_stream_t stream);
 /* The WEIGHT gradient of those convolutions (csrc/igemm_wgrad.hip; an additive entry, the ABI version stays):
  *   dw[n][c][ky][kx] (+)= sum over (b, y, x) of gy[b, n, y, x] * x[b, c, y*sy + ky - py, x*sx + kx - px], zero outside [0,Hi) x [0,Wi)
  * from two operands in the plane layout: x = bf16 [3][chunks][B*Hi*Wi][32] (chunks [in_chunk0, in_chunk0 + ceil(C/32)) of a buffer

@@ -82,6 +82,13 @@ class IgemmDesc(C.Structure):
                 ("tickets", C.c_void_p)]
 
 
+class IgemmTailPlan(C.Structure):
+    """ufr_igemm_tail_plan_t (include/ufr_hip.h), field for field."""
+    _fields_ = [("on", C.c_int), ("row_tiles", C.c_int), ("col_tiles", C.c_int), ("full_row_tiles", C.c_int), ("tail_row_tiles", C.c_int),
+                ("tail_row0", C.c_int), ("tail_rows", C.c_int), ("slices", C.c_int), ("slice_ktiles", C.c_int), ("ktiles", C.c_int),
+                ("workgroups", C.c_int), ("ws_floats", C.c_long), ("steps_before", C.c_int), ("steps_after", C.c_int)]
+
+
 UFR_IGEMM_WGRAD_MAX_TAPS = 49
 
 
@@ -208,6 +215,8 @@ SIGNATURES = {
     "ufr_raft_context_split_forward": [_vp, _vp, _vp, _i, _i, _i, _l, _vp],
     "ufr_raft_context_split_backward": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp],
     "ufr_igemm": [C.POINTER(IgemmDesc), _vp],
+    "ufr_igemm_tail_plan": [C.POINTER(IgemmDesc), _i, C.POINTER(IgemmTailPlan)],
+    "ufr_igemm_balanced": [C.POINTER(IgemmDesc), _i, _vp, _l, _vp],
     "ufr_igemm_wgrad": [C.POINTER(IgemmWgradDesc), _vp],
     "ufr_igemm_wgrad_dilated": [C.POINTER(IgemmWgradDesc), _i, _i, _vp],
     "ufr_flow_upscale4_forward": [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp],

@@ -225,8 +225,36 @@ struct Args {
   float* ws;                         // split-K slabs [sum of sk][M][Npad]
   int* tickets;                      // fused split-K reduction: one arrival counter per (phase, row tile, column tile), zero between launches
   int skip_out;                      // MEASUREMENT ONLY (UFR_IGEMM_DEBUG_SKIP_EPILOGUE=1): the accumulators are dropped -- what a launch costs without its epilogue
+  // re-cut last round (ufr_igemm_balanced; 0 = off): a 1-D grid of tl_full whole tiles, then the tiles of the row tiles from tl_rt0 on
+  // as tl_S slices of tl_per_k K tiles each, whose slabs [tl_S][tl_rows][Npad] start at row tl_row0 of the row grid
+  int tl_S, tl_full, tl_nt, tl_rt0, tl_row0, tl_rows, tl_per_k;
   Phase ph[4];
 };
+
+// The index map of a launch with a re-cut last round (ping-pong kernel, one phase): launch index -> (column tile, row tile, K slice);
+// returns whether the workgroup is a slice of a tail tile.  The hardware deals workgroups round-robin to the 8 XCDs in launch order,
+// so the two lists are dealt SEPARATELY, each XCD getting one contiguous run of either: appended to one list, the short workgroups
+// would all land on the last XCDs and the others would run two rounds of whole tiles.  Inside a run the slices of a tile vary
+// fastest, then its column tiles: they read the same activation rows.  (Placement is speed only: the slabs are added by a second launch.)
+__device__ __forceinline__ int xcd_before(int m, int x) { return (m >> 3) * x + min(m & 7, x); }   // j in [0, m) with j % 8 < x
+__device__ __forceinline__ bool tail_tile(const Args& a, int& bx, int& by, int& bz) {
+  const int orig = blockIdx.x, x = orig & 7;
+  const bool tail = orig >= a.tl_full;
+  const int lo = tail ? a.tl_full : 0, hi = tail ? (int)gridDim.x : a.tl_full;
+  // XCD x's run starts behind those of the XCDs before it; this workgroup is the XCD's (launch indices of [lo, orig) on x)-th
+  const int w = xcd_before(hi, x) - xcd_before(lo, x) + (orig >> 3) - ((lo + 7 - x) >> 3);
+  if (!tail) {
+    bz = 0;
+    by = w / a.tl_nt;
+    bx = w - by * a.tl_nt;
+    return false;
+  }
+  bz = w % a.tl_S;
+  const int rem = w / a.tl_S, rt = rem / a.tl_nt;
+  by = a.tl_rt0 + rt;
+  bx = rem - rt * a.tl_nt;
+  return true;
+}
 
 // The split-K sum of eight consecutive columns of one row: slabs `src + s * sstride`, s = 0 .. S - 1, added in ASCENDING order onto
 // zero (the slabs of up to eight slices are requested before the first is added: a deep split on a tiny grid -- 16 .. 32 slabs of a
@@ -294,7 +322,8 @@ __device__ __forceinline__ void sum_slabs(const float* src, long sstride, int S,
 // LDS array (a second __shared__ object beside an LDS-DMA staging array can de-pipeline the K loop).
 template <int NPL, int MT, int WGR, int BNT>
 __device__ __forceinline__ void igemm_write_out(const Args& a, const Phase& ph, f32x4 (&acc)[MT][4], float* lds_f32, int* flag, int z, int phase,
-                                                int tile_id, int bm0, int bm, int bn0, int bn, int wrow, int wcol, int lane, int wave) {
+                                                int tile_id, int bm0, int bm, int bn0, int bn, int wrow, int wcol, int lane, int wave,
+                                                bool tail_slice = false) {
   // C/D layout of the 16x16 forms: col = lane & 15, row = (lane >> 4) * 4 + reg
   if (a.skip_out) {                  // measurement only: the upper bound of what hiding the epilogue under the next tile's K loop could return
     float keep = 0.f;
@@ -305,8 +334,9 @@ __device__ __forceinline__ void igemm_write_out(const Args& a, const Phase& ph, 
     if (keep == 1.2345678e-30f && a.ws) a.ws[0] = keep;      // (never true in practice: keeps the K loop alive)
     return;
   }
-  if (a.splitk > 1) {
-    float* slab = a.ws + (long)z * a.g.M * a.Npad;
+  if (a.splitk > 1 || tail_slice) {
+    // (a slice of a re-cut last round, ufr_igemm_balanced: its slabs hold the tail's rows only and start at row tl_row0)
+    float* slab = a.ws + (tail_slice ? (long)z * a.tl_rows - a.tl_row0 : (long)z * a.g.M) * a.Npad;
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -636,7 +666,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);      // wave-uniform: scalar control flow
   const int wrow = BN_ == 128 ? (wave >> 1) * 64 : wave * 32, wcol = BN_ == 128 ? (wave & 1) * 64 : 0;
   int tx, ty, z;
-  xcd_tile(a.xcd, tx, ty, z);
+  bool tail_slice = false;                                                 // a K slice of a tile of the re-cut last round (tail_tile)
+  if (a.tl_S) tail_slice = tail_tile(a, tx, ty, z);
+  else xcd_tile(a.xcd, tx, ty, z);
   const int bm = ty * 256 + grp * 128, bn = tx * BN_;
   int phase = 0;
 #pragma unroll
@@ -645,7 +677,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int ks = z - a.zoff[phase];
   const Phase& ph = a.ph[phase];
   const int KC = a.KC, KT = ph.ntaps * KC;
-  const int kt0 = ks * a.per_k, kt1 = min(KT, kt0 + a.per_k);
+  const int per_k = tail_slice ? a.tl_per_k : a.per_k;
+  const int kt0 = ks * per_k, kt1 = min(KT, kt0 + per_k);
   const int nk = max(kt1 - kt0, 0);
   const long Min = (long)a.g.B * a.Hi * a.Wi;
   const long cstride = Min * 32;
@@ -788,7 +821,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const unsigned long long probe_c3 = probe ? __builtin_amdgcn_s_memtime() : 0;
   static_assert(4 * 32 * 68 * 4 <= 2 * PP_IMG * 2, "epilogue staging does not fit a group's activation images");
   igemm_write_out<NPL, MT, 256, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_pp + imgA0), reinterpret_cast<int*>(lds_pp), z, phase,
-                                     (phase * gridDim.y + ty) * gridDim.x + tx, ty * 256, bm, bn, bn, wrow, wcol, lane, wave);
+                                     (phase * gridDim.y + ty) * gridDim.x + tx, ty * 256, bm, bn, bn, wrow, wcol, lane, wave, tail_slice);
   if (probe && threadIdx.x == 0) {
     const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     if (wg < ufr_clock_probe_cap) {                                       // 8 words per workgroup: cycles at entry / exit, 100 MHz
@@ -1090,17 +1123,19 @@ constexpr int d33_lds_bytes() {
   return stage > epi ? stage : epi;
 }
 
-// Second stage of split-K: thread = (phase, row, 8 channels); the slabs are added in ascending order.
+// Second stage of split-K: thread = (phase, row, 8 channels); the slabs are added in ascending order.  A re-cut last round
+// (a.tl_S, one phase): rows [tl_row0, tl_row0 + tl_rows) only, slabs [tl_S][tl_rows][Npad].
 __global__ __launch_bounds__(256) void igemm_reduce_kernel(const Args a) {
   const int n8 = a.Npad / 8;
-  const long total = (long)a.nphase * a.g.M * n8;
+  const int rows = a.tl_S ? a.tl_rows : a.g.M, row0 = a.tl_S ? a.tl_row0 : 0;
+  const long total = (long)a.nphase * rows * n8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int n0 = (int)(i % n8) * 8;
     const long rest = i / n8;
-    const int row = (int)(rest % a.g.M), phase = (int)(rest / a.g.M);
+    const int r = (int)(rest % rows), row = row0 + r, phase = (int)(rest / rows);
     if (n0 >= a.e.Nchunks32 * 32) continue;
     float v[8];
-    sum_slabs(a.ws + ((long)a.zoff[phase] * a.g.M + row) * a.Npad + n0, (long)a.g.M * a.Npad, a.sk[phase], v);
+    sum_slabs(a.ws + ((long)a.zoff[phase] * rows + r) * a.Npad + n0, (long)rows * a.Npad, a.tl_S ? a.tl_S : a.sk[phase], v);
     epilogue_store8(a.e, out_pixel(a.g, row, a.ph[phase].oy0, a.ph[phase].ox0), n0, v);
   }
 }
@@ -1120,7 +1155,10 @@ std::atomic<int> g_variant_fallbacks{0};     // launches that asked for variant 
 }
 extern "C" int ufr_igemm_variant_fallbacks(void) { return g_variant_fallbacks.load(); }
 
-extern "C" int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream) {
+namespace {
+// ufr_igemm; with `tp` (a plan that is ON, ufr_igemm_balanced) the ping-pong launch whose last round is re-cut into K slices with
+// slabs in `tws`, and the reduce launch over the tail's rows.
+int igemm_run(const ufr_igemm_desc* d, const ufr_igemm_tail_plan_t* tp, float* tws, ufr_stream_t stream) {
   UFR_REQUIRE(d, "igemm: null descriptor");
   UFR_REQUIRE(d->x && d->w, "igemm: null operand");
   UFR_REQUIRE(d->B > 0 && d->Hi > 0 && d->Wi > 0 && d->Hr > 0 && d->Wr > 0 && d->Ho > 0 && d->Wo > 0, "igemm: bad grid");
@@ -1167,6 +1205,12 @@ extern "C" int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream) {
   static const int skip_out = [] { const char* e = getenv("UFR_IGEMM_DEBUG_SKIP_EPILOGUE"); return e ? atoi(e) : 0; }();
   a.skip_out = skip_out == 1;
   a.e.nostore = skip_out == 2;
+  a.tl_S = a.tl_full = a.tl_nt = a.tl_rt0 = a.tl_row0 = a.tl_rows = a.tl_per_k = 0;
+  if (tp) {
+    a.tl_S = tp->slices; a.tl_full = tp->full_row_tiles * tp->col_tiles; a.tl_nt = tp->col_tiles; a.tl_rt0 = tp->full_row_tiles;
+    a.tl_row0 = tp->tail_row0; a.tl_rows = tp->tail_rows; a.tl_per_k = tp->slice_ktiles;
+    a.ws = tws;
+  }
   a.xcd = 1;                              // XCD-aware tile order (off: +0.2 ms per iteration, profiles/r2_bench_engine_v4_no_xcd_order)
   a.korder = d->k_order ? 1 : 0;
   for (int z = 0; z < 4; ++z) {
@@ -1286,7 +1330,7 @@ extern "C" int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream) {
     if (use_buf) igemm_glds_kernel<64, 128, false, true><<<g64, 256, 0, st>>>(a);
     else igemm_glds_kernel<64, 128><<<g64, 256, 0, st>>>(a);
   } else if ((variant == 6 || variant == 7) && bn == BN) {           // ping-pong: 256-row tiles, two wave groups half a step apart
-    const dim3 gpp(d->Npad / BN, (unsigned)((M + 255) / 256), nz);
+    const dim3 gpp = tp ? dim3(tp->workgroups) : dim3(d->Npad / BN, (unsigned)((M + 255) / 256), nz);
     if (use_buf) igemm_pp_kernel<128, true><<<gpp, 512, pp_lds_bytes(128), st>>>(a);
     else igemm_pp_kernel<128><<<gpp, 512, pp_lds_bytes(128), st>>>(a);
   } else if (variant == 5 && bn == BN) {           // register-held fragments, DMA of the next tile under the MFMAs
@@ -1299,9 +1343,68 @@ extern "C" int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream) {
     else igemm_glds_kernel<128, 64><<<grid, 256, 0, st>>>(a);
   }
   int rc = ufr::launched("igemm_kernel");
-  if (rc != UFR_OK || d->splitk == 1 || d->no_reduce || a.tickets) return rc;     // no_reduce: the caller's next kernel adds the slabs itself;
+  if (rc != UFR_OK || (!tp && (d->splitk == 1 || d->no_reduce || a.tickets))) return rc;   // no_reduce: the caller's next kernel adds the slabs itself;
                                                                                   // tickets: the last workgroup of every tile already has
-  const long total = (long)d->nphase * M * (d->Npad / 8);
+  const long total = tp ? (long)tp->tail_rows * (d->Npad / 8) : (long)d->nphase * M * (d->Npad / 8);
   igemm_reduce_kernel<<<ufr::stream_grid(total, 256), 256, 0, st>>>(a);
   return ufr::launched("igemm_reduce_kernel");
+}
+}  // namespace
+
+extern "C" int ufr_igemm(const ufr_igemm_desc* d, ufr_stream_t stream) { return igemm_run(d, nullptr, nullptr, stream); }
+
+extern "C" int ufr_igemm_tail_plan(const ufr_igemm_desc* d, int resident_workgroups, ufr_igemm_tail_plan_t* plan) {
+  UFR_REQUIRE(d && plan, "igemm tail plan: null argument");
+  UFR_REQUIRE(resident_workgroups >= 0 && resident_workgroups <= (1 << 20), "igemm tail plan: bad resident workgroup count");
+  UFR_REQUIRE(d->B > 0 && d->Hr > 0 && d->Wr > 0 && d->KC > 0 && d->Npad > 0 && d->Npad % 64 == 0 && d->nphase >= 1 && d->nphase <= 4,
+              "igemm tail plan: bad descriptor");
+  const long M = (long)d->B * d->Hr * d->Wr;
+  UFR_REQUIRE(M < (1L << 30), "igemm tail plan: too many pixels");
+  UFR_REQUIRE(d->phase[0].ntaps >= 1 && d->phase[0].ntaps <= UFR_IGEMM_MAX_TAPS && (long)d->phase[0].ntaps * d->KC < (1L << 24),
+              "igemm tail plan: bad phase");
+  *plan = ufr_igemm_tail_plan_t{};
+  const int R = resident_workgroups ? resident_workgroups : 256;          // one ping-pong workgroup per CU, 256 CUs
+  const int Mt = (int)((M + 255) / 256), ktiles = d->phase[0].ntaps * d->KC;
+  plan->row_tiles = Mt; plan->ktiles = ktiles;
+  plan->full_row_tiles = Mt;
+  if (d->Npad % 128 != 0 || d->nphase != 1 || d->variant != 6 || d->products != 6 || d->tickets || d->no_reduce || d->tail || d->splitk > 1)
+    return UFR_OK;
+  const int Nt = d->Npad / 128;
+  plan->col_tiles = Nt;
+  const long T = (long)Mt * Nt;
+  const long q = T / R;
+  plan->steps_before = (int)((T + R - 1) / R) * (ktiles + 6);             // a workgroup = its K steps + ~6 for the epilogue (splitk_for)
+  plan->steps_after = plan->steps_before;
+  if (q == 0 || T % R == 0) return UFR_OK;
+  const int full = (int)(q * R / Nt), tail_rt = Mt - full;
+  const long tail_tiles = (long)tail_rt * Nt;
+  long S = R / tail_tiles;                                                // fill the chip once ...
+  if (S > ktiles / 8) S = ktiles / 8;                                     // ... with slices of at least 8 K tiles ...
+  if (S > 8) S = 8;                                                       // ... and at most 8 slabs
+  if (S < 2) return UFR_OK;
+  const int per = (int)((ktiles + S - 1) / S);
+  const int after = (int)q * (ktiles + 6) + (per + 6) + 10;               // the full rounds, one short round, the reduce launch (~10)
+  if (after > plan->steps_before) return UFR_OK;                          // the kernel's saving does not pay for the reduce launch
+  plan->on = 1;
+  plan->full_row_tiles = full; plan->tail_row_tiles = tail_rt;
+  plan->tail_row0 = full * 256; plan->tail_rows = (int)(M - (long)full * 256);
+  plan->slices = (int)S; plan->slice_ktiles = per;
+  plan->workgroups = (int)((long)full * Nt + tail_tiles * S);
+  plan->ws_floats = S * (long)plan->tail_rows * d->Npad;
+  plan->steps_after = after;
+  return UFR_OK;
+}
+
+extern "C" int ufr_igemm_balanced(const ufr_igemm_desc* d, int resident_workgroups, float* ws, long ws_floats, ufr_stream_t stream) {
+  UFR_REQUIRE(d, "igemm: null descriptor");
+  UFR_REQUIRE(resident_workgroups >= 0, "igemm (balanced): bad resident workgroup count");
+  int R = resident_workgroups, dev = 0;
+  if (!R && (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&R, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || R < 1))
+    return ufr::fail(UFR_ELAUNCH, "igemm (balanced): no current device");
+  ufr_igemm_tail_plan_t plan;
+  const int rc = ufr_igemm_tail_plan(d, R, &plan);
+  if (rc != UFR_OK) return rc;
+  UFR_REQUIRE(!plan.on || (ws && ws_floats >= plan.ws_floats), "igemm (balanced): workspace of %ld floats needed, %ld given", plan.ws_floats,
+              ws ? ws_floats : 0L);
+  return igemm_run(d, plan.on ? &plan : nullptr, ws, stream);   // (plan off: ufr_igemm itself, nothing extra launched)
 }

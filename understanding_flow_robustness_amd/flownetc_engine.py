@@ -196,7 +196,8 @@ class FlowNetCHeadEngine:
         launches = [ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
                     for wi, x, c0, rows, out_hw, S, kw in plans]
         self.fwd = {k: launches[i] for k, i in fwd.items()}
-        self.bwd = {k: launches[i] for k, i in bwd.items()}
+        self.plain = {}                         # (table tag, name): the plain twin of a launch that runs with its last round re-cut
+        self.bwd = {k: self._with_tail(("full", k), launches[i], plans[i][:5], plans[i][6], plans[i][5]) for k, i in bwd.items()}
         self._plans = {("fwd", k): plans[i] for k, i in fwd.items()}
         self._plans.update({("bwd", k): plans[i] for k, i in bwd.items()})
         self._band, self.fwd_band, self.bwd_band = None, {}, {}
@@ -215,6 +216,26 @@ class FlowNetCHeadEngine:
         self.up_G = {6: (self.G_cat5, 32), 5: (self.G_cat4, 24), 4: (self.G_cat3, 12), 3: (self.G_cat2, 6)}
 
     # ------------------------------------------------------------------------------------------------ conv1-3
+    def _with_tail(self, key, plain, args, kw, S, resident=None):
+        """`plain`, or -- when `ufr_igemm_tail_plan` says it pays -- the same launch with the tiles of its under-filled last round
+        split over K (igemm.make_launch `balance`).  The plain launch then stays in `self.plain[key]` for `backward(tail_split=False)`.
+        `resident`: workgroups the chip holds (None: its CU count).  Tests pass a small number so that small grids have a tail; the
+        split-K factor `S` was sized for the real chip, so with the override the plan alone decides."""
+        self.plain.pop(key, None)
+        if S != 1 and resident is None:
+            return plain
+        wi, x, c0, rows, out_hw = args
+        launch = ig.make_launch(wi, x, c0, rows, out_hw, ws=self.ws, balance=True, resident=resident, **kw)
+        if launch.tail_plan is None:
+            return plain
+        self.plain[key] = plain
+        return launch
+
+    def tail_launches(self):
+        """[(table tag, name, plan)] of the launches that run with a re-cut last round."""
+        tables = {"full": self.bwd, "band": self.bwd_band, "rest": self.bwd_rest}
+        return [(tag, name, tables[tag][name].tail_plan) for tag, name in sorted(self.plain)]
+
     def _variant_for(self, wi):
         """The igemm form of a launch: the 128-column forms as `UFR_IGEMM_PIPE` says, 64-column launches single-stage."""
         return self._pipe_variant if wi.Npad % 128 == 0 else 2
@@ -498,12 +519,14 @@ class FlowNetCHeadEngine:
             return
         self._band, self.fwd_band, self.bwd_band = band, {}, {}
         self.bwd_band_wide, self.bwd_rest, self._band_plans, self._pf_band = {}, {}, {}, {}
+        self.plain = {k: v for k, v in self.plain.items() if k[0] == "full"}
         if not band.width:
             return
         W = self.W
         if band.width % 32 or band.width > W:
             raise ValueError("band width must be a multiple of 32 pixels inside the frame")
         origin = band.win[:, 1]                                   # int32 view, 8 elements per pair
+        resident = getattr(band, "tail_resident", None)           # (tests: a small chip, so that small grids have a tail round)
 
         def derive(kind, name, ls_rows, ls_in):
             wi, x, c0, rows, out_hw, S, kw = self._plans[(kind, name)]
@@ -517,7 +540,10 @@ class FlowNetCHeadEngine:
             Sb = ig.splitk_for(M, wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target)
             if len(wi.phases) * Sb * M * wi.Npad > self.ws.numel():
                 Sb = 1
-            return ig.make_launch(wi, x, c0, rows_b, out_hw, splitk=Sb, ws=self.ws if Sb > 1 else None, **kw, **extra)
+            launch = ig.make_launch(wi, x, c0, rows_b, out_hw, splitk=Sb, ws=self.ws if Sb > 1 else None, **kw, **extra)
+            if kind == "bwd":
+                launch = self._with_tail(("band", name), launch, (wi, x, c0, rows_b, out_hw), dict(kw, **extra), Sb, resident)
+            return launch
 
         for name, (ls_rows, _) in self._FWD_BAND.items():
             if ("fwd", name) in self._plans:
@@ -550,7 +576,9 @@ class FlowNetCHeadEngine:
             if len(wi.phases) * S * M * wi.Npad > self.ws.numel():
                 S = 1
             self._band_plans[name] = (wi, x, c0, rows, out_hw, kw)
-            return ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
+            launch = ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
+            return self._with_tail(("rest" if name.endswith(" rest") else "band", name), launch, (wi, x, c0, rows, out_hw), kw, S,
+                                   getattr(band, "tail_resident", None))
 
         for k, (lead, ls) in self._SPLIT_DECONV.items():
             src, chunk0, _, Gd, _, rows = self.tail_args[k]
@@ -573,7 +601,7 @@ class FlowNetCHeadEngine:
                 raise ValueError("correlation band: a multiple of 8 pixels inside the band")
             for name in ("conv3_1", "conv_redir"):
                 wi, x, c0, rows, out_hw, _, kw = self._plans[("bwd", name)]
-                self.bwd_band_wide[name] = self.bwd_band[name]
+                self.bwd_band_wide[name] = self.plain.get(("band", name), self.bwd_band[name])     # (the comparison leg stays plain)
                 kw = dict(kw, row_band=(band.win[:, 2], 8, 8), in_band=(origin, 8, 8, band.width // 8))
                 self.bwd_band[name] = planned(name, wi, x, c0, (rows[0], cw // 8), out_hw, kw)
 
@@ -777,7 +805,7 @@ class FlowNetCHeadEngine:
             self._pf_forward(k)
         return self.flow[2]
 
-    def backward(self, g_flow2: torch.Tensor, band=None, fused_window: bool = True, skip_unread: bool = True):
+    def backward(self, g_flow2: torch.Tensor, band=None, fused_window: bool = True, skip_unread: bool = True, tail_split: bool = True):
         """d loss / d flow2 -> (d/d conv2a, d/d conv3a, d/d conv3b), all NCHW float32 (static buffers).
         With a band: the data gradients of conv5, conv4_1, conv4, conv3_1 and conv_redir run on the band's columns and the
         correlation's adjoint on the window's cells (only those are read behind a windowed prefix).  When the band carries
@@ -786,9 +814,12 @@ class FlowNetCHeadEngine:
         `skip_unread` (with a band and `fused_window`): gradients that only a banded or windowed launch reads are produced where
         it reads them (`_attach_unread`; predict_flow2's conv2 chunks straight into the window prefix's addend when that prefix
         runs on the engine) -- G_cat2[0:4] is then not written, G_cat3[0:8], G_cat4[0:16], G_in31 and G_c3a outside those regions
-        keep stale values.  False: every gradient sum in full, as the autograd Function and the training path need them."""
+        keep stale values.  False: every gradient sum in full, as the autograd Function and the training path need them.
+        `tail_split`: launches whose under-filled last round is re-cut over K (`_with_tail`) run in that form; False: their plain
+        twins, today's launches (the A/B leg; the tail's rows differ by the order of a float32 sum)."""
         L.require_hip(g_flow2, "g_flow2")
         B = self.B
+        run = lambda table, tag, name: (table[name] if tail_split else self.plain.get((tag, name), table[name]))()
         banded = band is not None and bool(band.width)
         if band is not None:
             self.attach_band(band)
@@ -821,12 +852,12 @@ class FlowNetCHeadEngine:
             self._up_backward(k + 1)                               # -> d/d flow(K+1)
             region = None
             if skip and k + 1 in self._pf_band:                    # cat(K+1)'s leading chunks: only the band is read
-                self.bwd_band[f"deconv{k}"]()
-                self.bwd_rest[f"deconv{k} rest"]()
+                run(self.bwd_band, "band", f"deconv{k}")
+                run(self.bwd_rest, "rest", f"deconv{k} rest")
                 head, ls = self._pf_band[k + 1]
                 region = (head, L.UFR_PF_REGION_BAND, band.win[:, 1], 8, ls, self.grid[ls][0], band.width // ls, 0, None)
             else:
-                self.bwd[f"deconv{k}"]()                           # writes the gradient sum of cat(K+1)
+                run(self.bwd, "full", f"deconv{k}")                # writes the gradient sum of cat(K+1)
             self._deconv_tail(k)
             self._pf_backward(k + 1, self.g_flow[k + 1], accumulate=True, finalize=fin(k + 1), region=region)
         Gs, act, out, chunk0, chunks = gz[5]
@@ -835,17 +866,19 @@ class FlowNetCHeadEngine:
         self._up_backward(6)
         self._pf_backward(6, self.g_flow[6], accumulate=False)      # G_c6 = predict_flow6^T; deconv5's adjoint adds to it
         for name in ("deconv5", "conv6_1", "conv6", "conv5_1"):
-            self.bwd[name]()
+            run(self.bwd, "full", name)
         if not self.siamese:                    # FlowNetS trunk: conv3_1's data gradient IS d/d conv3
             for name in ("conv5", "conv4_1", "conv4", "conv3_1"):
-                self.bwd[name]()
+                run(self.bwd, "full", name)
             self.G_in31.to_nchw(256, 0, out=self.g_c3a)
             return self.g_c2a, self.g_c3a, None
         for name in ("conv5", "conv4_1", "conv4", "conv3_1", "conv_redir"):
             if banded and not skip and name in self.bwd_band_wide:
                 self.bwd_band_wide[name]()
+            elif banded:
+                run(self.bwd_band, "band", name)
             else:
-                (self.bwd_band if banded else self.bwd)[name]()
+                run(self.bwd, "full", name)
         # conv_redir's input and the correlation's two inputs
         gw = getattr(band, "g3_window", None) if (band is not None and fused_window) else None
         h8, w8 = self.grid[8]

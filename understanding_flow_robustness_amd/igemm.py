@@ -299,10 +299,17 @@ def deconv_backward_weights(weight: torch.Tensor, padding: int) -> WeightImage:
 class Launch:
     """One prepared `ufr_igemm` call: the descriptor plus references that keep its tensors alive."""
 
-    def __init__(self, desc, keep):
+    def __init__(self, desc, keep, tail_plan=None, resident=0, tail_ws=None):
         self.desc, self._keep = desc, keep
+        # `make_launch(balance=True)` whose plan came back on (csrc/igemm.hip ufr_igemm_balanced): the full rounds as they are, the
+        # tiles of the under-filled last round as K slices with slabs in `tail_ws`; None: the plain call
+        self.tail_plan, self._resident, self._tail_ws = tail_plan, int(resident), tail_ws
 
     def __call__(self):
+        if self.tail_plan is not None:
+            L.check(L.lib().ufr_igemm_balanced(C.byref(self.desc), self._resident, L.ptr(self._tail_ws), self._tail_ws.numel(), L.stream()),
+                    "igemm (balanced)")
+            return
         L.check(L.lib().ufr_igemm(C.byref(self.desc), L.stream()), "igemm")
 
     def algorithmic_bytes(self) -> float:
@@ -413,13 +420,17 @@ def make_launch(wi: WeightImage, x: Planes, in_chunk0: int, rows_hw, out_hw, *, 
                 slope: float = LEAKY, splitk: int = 1, ws: torch.Tensor | None = None, row_band=None, in_band=None,
                 products: int | None = None, variant: int = 0, tail: GradSum | None = None, tail_n0: int = 0, tail_chunk0: int = 0,
                 tail_accumulate: bool = False, out_rowmajor=None, planes_chunks: int = 0, f32_first_chunk: int = 0,
-                no_reduce: bool = False, fuse_reduce: bool | None = None) -> Launch:
+                no_reduce: bool = False, fuse_reduce: bool | None = None, balance: bool = False, resident: int | None = None) -> Launch:
     """Descriptor for `wi` applied to the chunks [in_chunk0, in_chunk0 + KC) of `x`.
     rows_hw = (Hr, Wr) row grid; out_hw = (Ho, Wo) output grid.  row_band = (origins int32 tensor, element stride, divisor):
     tail / tail_n0: the launch's output columns >= tail_n0 are a LATER layer's partial sum over these input chunks and leave raw
     into `tail` (chunk `tail_chunk0` on; `tail_accumulate`: added onto it); that layer's own launch passes it as `add`.
     the row grid's columns start at origins[b*stride] // divisor.  in_band = (origins, stride, divisor, width): input
-    columns outside [origin, origin + width) read as zero.  bias given -> forward epilogue (bias + LeakyReLU)."""
+    columns outside [origin, origin + width) read as zero.  bias given -> forward epilogue (bias + LeakyReLU).
+    balance: ask `ufr_igemm_tail_plan` (for `resident` workgroups on the chip; None: the device's CU count, 256 without a device)
+    whether the launch's under-filled last round is worth re-cutting over K; when the plan is on the Launch calls
+    `ufr_igemm_balanced` with slabs in `ws` (when it holds the plan's `ws_floats`) or in a workspace of its own, and carries the
+    plan as `.tail_plan`; when it is off the Launch is the plain one."""
     if RECORD is not None:
         RECORD.append(dict(wi=wi, x=x, in_chunk0=in_chunk0, rows=tuple(rows_hw), out_hw=tuple(out_hw), splitk=splitk, variant=variant,
                            kw=dict(out_planes=out_planes, out_chunk0=out_chunk0, out_f32=out_f32, out_f32_chunk0=out_f32_chunk0, bias=bias,
@@ -503,7 +514,27 @@ def make_launch(wi: WeightImage, x: Planes, in_chunk0: int, rows_hw, out_hw, *, 
     d.products = int(_PRODUCTS[-1] if products is None else products)
     d.k_order = int(wi.k_order)
     d.variant = int(variant)               # 0 / 2 = single-stage tiles, 4 = 64 x 128, 5 = pipelined, 6 = ping-pong (csrc/igemm.hip)
+    if balance:
+        R = int(resident) if resident else resident_workgroups(x.t.device)
+        plan = tail_plan(d, R)
+        if plan.on:
+            tws = ws if (ws is not None and ws.dtype == torch.float32 and ws.numel() >= plan.ws_floats) else \
+                torch.empty(plan.ws_floats, dtype=torch.float32, device=x.t.device)
+            return Launch(d, keep + [tws], tail_plan=plan, resident=R, tail_ws=tws)
     return Launch(d, keep)
+
+
+def resident_workgroups(device) -> int:
+    """Ping-pong workgroups the chip holds at once: one per CU (256 where there is no device to ask)."""
+    device = torch.device(device)
+    return int(torch.cuda.get_device_properties(device).multi_processor_count) if device.type == "cuda" else 256
+
+
+def tail_plan(desc, resident: int = 0) -> "L.IgemmTailPlan":
+    """`ufr_igemm_tail_plan` of a descriptor: host arithmetic, no device needed."""
+    plan = L.IgemmTailPlan()
+    L.check(L.lib().ufr_igemm_tail_plan(C.byref(desc), int(resident), C.byref(plan)), "igemm tail plan")
+    return plan
 
 
 def splitk_for(M: int, Npad: int, ktiles: int, phases: int = 1, target: int = 768, phase_ktiles=None, bm: int = 128,

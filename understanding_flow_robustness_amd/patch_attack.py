@@ -80,7 +80,7 @@ class PatchAttackStep:
 
     def __init__(self, flow_net, args, batch, height, width, device="cuda:0", shared_patch=True,
                  exchange: ShardedExchange | None = None, use_graph=True, warmup=3, use_cone=None, patch_hw=None,
-                 sum_groups=1, skip_unread=True, corr_changed=True):
+                 sum_groups=1, skip_unread=True, corr_changed=True, tail_split=True, tail_resident=None):
         L.lib()   # fail loudly, now, if libufr_hip.so is missing
         self.net, self.args = flow_net, args
         # the engine's banded backward writes gradients that only the band / the window reads where they are read
@@ -89,6 +89,10 @@ class PatchAttackStep:
         # later iterations recompute only the cost-volume entries the window's features reach (flownetc_engine.py `forward`);
         # False: every row and displacement of the columns around the window
         self.corr_changed = bool(corr_changed)
+        # data gradients whose last round of 256 x 128 tiles is under-filled run with that round's tiles split over K
+        # (flownetc_engine.py `_with_tail`); False: the plain launches.  tail_resident: the chip's resident workgroups as the plan
+        # sees them (None: the CU count; tests pass a small number so that a small frame has such a round)
+        self.tail_split, self.tail_resident = bool(tail_split), tail_resident
         self.B, self.H, self.W = batch, height, width
         self.dev = torch.device(device)
         self.shared = shared_patch
@@ -297,6 +301,8 @@ class PatchAttackStep:
                              cone_hw=(wh, ww))
             if bw and corr_band_width(ww) <= bw:   # conv3_1's / conv_redir's data gradients: the correlation's reach is enough
                 self.band.corr_width = corr_band_width(ww)
+            if self.tail_resident:
+                self.band.tail_resident = int(self.tail_resident)
             if bw and os.environ.get("UFR_INCREMENTAL", "1") != "0":
                 self.band.inc_layers = tuple(getattr(self.net, "INCREMENTAL_LAYERS", ()))
 
@@ -386,7 +392,8 @@ class PatchAttackStep:
                 if self.band is not None:        # the engine writes conv3's window gradient itself (fused correlation adjoint)
                     self.band.g3_window, self.band.g3_margin = gw3, m3
                     self.band.eng_window, self.band.g2_margin = True, m2
-                g2a, g3a, g3b = self.eng.backward(g_flow2.contiguous(), self.band, skip_unread=self.skip_unread)
+                g2a, g3a, g3b = self.eng.backward(g_flow2.contiguous(), self.band, skip_unread=self.skip_unread,
+                                                  tail_split=self.tail_split)
                 if g2a is not None:
                     self._win_copy(lib.ufr_window_gather, g2a, gw2, B, 128, H // ls2, W // ls2, ls2, m2)
                 if g3a is not None:

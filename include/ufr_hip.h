@@ -307,6 +307,12 @@ int ufr_flow_loss(const float* flow, const float* target, float* grad_flow, floa
  *   UFR_EUNSUPPORTED when B * ceil(h/16) * ceil(w/16) > UFR_LOSS_PARTIALS (the caller keeps the three-pass form). */
 int ufr_flow2_upsampled_loss(const float* flow2, float flow_scale, const float* target, float* grad_flow2, float* loss, int B,
                              int h, int w, int kind, float weight, float* partials, ufr_stream_t stream);
+/* The same launch as a pass over the target: the x4 source index and weights of a row / column are evaluated once per workgroup,
+ * the gather walks the taps of non-zero weight only, the region pixels that reach no cell of the tile are not evaluated.  Same
+ * tiles, same pixel-to-thread assignment, same per-pixel arithmetic, same order of additions in the gather and in the loss sum:
+ * grad_flow2 AND the loss are bit-identical to the entry above on finite inputs. */
+int ufr_flow2_upsampled_loss_fast(const float* flow2, float flow_scale, const float* target, float* grad_flow2, float* loss, int B,
+                                  int h, int w, int kind, float weight, float* partials, ufr_stream_t stream);
 
 /* ---- RAFT SepConvGRU gate arithmetic -----------------------------------------------------------
  * replaces the elementwise half of models/raft/update.py:61-73 (10 launches forward per half-step):
@@ -886,6 +892,24 @@ int ufr_flow_head_planes_forward(const void* planes, long plane_stride, int chun
  * wmf: bf16 [chunks][3][2][16][32] (plane p of w[o][32 ch + c][k] at n = 2k + o, zeros for n >= 18). */
 int ufr_flow_head_planes_forward_mfma(const void* planes, long plane_stride, int chunk0, int chunks, const void* wmf, int w_chunks,
                                       const float* bias, float* out, int B, int H, int W, ufr_stream_t stream);
+/* The same convolution for grids too small to fill the chip with one workgroup per tile (1/64 .. 1/16 of the headline's frame): the
+ * chunk slices that ufr_flow_head_planes_forward_mfma keeps inside a workgroup spread over the grid.
+ *   ufr_flow_head_split_plan            what the unsplit entry runs on this grid: `slices` = the partial sums it adds per pixel,
+ *                                       `starved` = 1 where B * ceil(H/4) * ceil(W/32) < 256 (its own test for falling to its
+ *                                       smallest tile; the engines split exactly there), `partial_floats` = slices * B*H*W * 18.
+ *   ufr_flow_head_planes_forward_split  T[slice][pixel][n = 2k + o] of every chunk slice -> `partials` (float32, no bias, no
+ *                                       gather).  `slices` must be the plan's: another count changes per = ceil(chunks / slices),
+ *                                       the order of additions and so the last bits, and is refused.
+ *   ufr_flow_head_split_finish          flow [B,2,H,W] = bias + the running sum over slices (ascending) and taps (ascending) of T,
+ *                                       the order of the unsplit entry: bit-identical to it.  With `up_planes` the launch also does
+ *                                       what ufr_flow_up_planes_forward(flow, up_w, up_bias, up_planes, ..) would do next, the same
+ *                                       arithmetic from the sums it holds (up_bias may be NULL); NULL = the sum only. */
+int ufr_flow_head_split_plan(int B, int H, int W, int chunks, int* slices, int* starved, long* partial_floats);
+int ufr_flow_head_planes_forward_split(const void* planes, long plane_stride, int chunk0, int chunks, const void* wmf, int w_chunks,
+                                       float* partials, long partial_floats, int slices, int B, int H, int W, ufr_stream_t stream);
+int ufr_flow_head_split_finish(const float* partials, long partial_floats, int slices, const float* bias, float* flow,
+                               const float* up_w, const float* up_bias, void* up_planes, long up_plane_stride, int up_chunk, int B,
+                               int H, int W, ufr_stream_t stream);
 /* The two flow channels of a ConvTranspose2d(Cin, Cout, 4, 2, 1) data gradient (models/FlowNetC.py:162-183: the last two
  * input channels of deconvK are the upsampled flow), same per-pixel GEMM + gather: grad_planes = the masked output gradient
  * on the fine grid [2H, 2W] (chunks chunk0 .. chunk0 + chunks), wmf as above with n = 2 (4 ky + kx) + o for the weights

@@ -584,6 +584,170 @@ extern "C" int ufr_flow2_upsampled_loss(const float* flow2, float flow_scale, co
   return ufr::launched("flow2_upsampled_loss_kernel");
 }
 
+// The same launch as a pass over the target (ufr_flow2_upsampled_loss_fast).  Tiles, the pixel-to-thread assignment (i = tid +
+// 256 k over the 72 x 72 region, so every thread adds its loss terms in the order above), the per-pixel arithmetic and the gather's
+// order of additions are the kernel's above: gradient and loss are bit-identical.  What is gone is the repeated work:
+//   - the x4 source index and weight of a row / column are evaluated once per workgroup into LDS, not per pixel and per tap;
+//   - cell c has a weight on the pixels 4c - 2 .. 4c + 5 only (src in (c - 1, c + 1); the clamps at both borders stay inside that
+//     range), so the gather walks 8 x 8 taps with the column weights in registers instead of testing 10 x 10 candidates;
+//   - the region's outer two pixels per side reach no cell of the tile and own no loss term: they are not evaluated, and the
+//     gradient tile shrinks to 68 x 68 -- 40 KB of LDS per workgroup, four per CU instead of three (960 workgroups at the headline's
+//     size: one round over 256 CUs instead of two);
+//   - the target of three pixels per thread is in flight before the first of them is evaluated.
+// (A tap of weight zero used to add 0 * g: the sums differ from the kernel above only where g is not finite.)
+constexpr int F2_G = 4 * F2_T + 4, F2_C = F2_T + 2;                        // gradient tile side (pixels); cells those pixels read
+__global__ __launch_bounds__(256) void flow2_upsampled_loss_fast_kernel(const float* __restrict__ flow2, float flow_scale,
+                                                                        const float* __restrict__ target,
+                                                                        float* __restrict__ gflow2, float* __restrict__ partials,
+                                                                        int B, int h, int w, int kind, float weight) {
+  __shared__ float f2[2][F2_C][F2_C];                                      // cells c0 - 1 .. c0 + 16 (indices clamped), x flow_scale
+  __shared__ float g[2][F2_G][F2_G];                                       // d loss / d flow on the pixels 4 c0 - 2 .. 4 c0 + 65
+  __shared__ float tl[2][F2_G];                                            // [axis y, x][pixel of g]: l1
+  __shared__ unsigned char ti[2][2][F2_G];                                 // i0, i1 relative to cell c0 - 1; 255 = outside the frame
+  __shared__ float red[4];
+  const int tid = threadIdx.x, b = blockIdx.z;
+  const int cy0 = blockIdx.y * F2_T, cx0 = blockIdx.x * F2_T;
+  const int H = 4 * h, W = 4 * w;
+  const long HW = (long)H * W, hw = (long)h * w;
+  const float invn = weight / (float)((long)B * HW);
+  for (int i = tid; i < 2 * F2_C * F2_C; i += 256) {
+    const int c = i / (F2_C * F2_C), r = i - c * F2_C * F2_C, yy = r / F2_C, xx = r - yy * F2_C;
+    const int cy = min(max(cy0 - 1 + yy, 0), h - 1), cx = min(max(cx0 - 1 + xx, 0), w - 1);
+    f2[c][yy][xx] = flow2[((long)b * 2 + c) * hw + (long)cy * w + cx] * flow_scale;
+  }
+  if (tid < 2 * F2_G) {
+    const int axis = tid / F2_G, r = tid - axis * F2_G;
+    const int c0 = axis ? cx0 : cy0, n = axis ? w : h, p = 4 * c0 - 2 + r;
+    int i0 = 255 + c0 - 1, i1 = 255 + c0 - 1;
+    float l1 = 0.f;
+    if (p >= 0 && p < 4 * n) up4_source(p, n, i0, i1, l1);
+    ti[axis][0][r] = (unsigned char)(i0 - (c0 - 1));
+    ti[axis][1][r] = (unsigned char)(i1 - (c0 - 1));
+    tl[axis][r] = l1;
+  }
+  __syncthreads();
+  const int py0 = 4 * cy0 - 2, px0 = 4 * cx0 - 2;                          // pixel of g[.][0][0]
+  float part = 0.f;
+  int ry = tid / F2_R, rx = tid - ry * F2_R;                               // region pixel i = tid + 256 k, as above
+  constexpr int F2_K = (F2_R * F2_R + 255) / 256;                          // 21 pixels per thread (the last round is partial)
+  for (int k0 = 0; k0 < F2_K; k0 += 3) {
+    int gy[3], gx[3];
+    bool store[3], live[3], owned[3];
+    float tu[3], tv[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      gy[j] = ry - 2;
+      gx[j] = rx - 2;
+      store[j] = ry < F2_R && gy[j] >= 0 && gy[j] < F2_G && gx[j] >= 0 && gx[j] < F2_G;
+      live[j] = store[j] && ti[0][0][store[j] ? gy[j] : 0] != 255 && ti[1][0][store[j] ? gx[j] : 0] != 255;
+      owned[j] = ry >= 4 && ry < F2_R - 4 && rx >= 4 && rx < F2_R - 4;
+      tu[j] = tv[j] = 0.f;
+      if (live[j]) {
+        const long o0 = ((long)b * 2) * HW + (long)(py0 + gy[j]) * W + (px0 + gx[j]);
+        tu[j] = target[o0];
+        tv[j] = target[o0 + HW];
+      }
+      rx += 256 - 3 * F2_R;                                                // i += 256 = 3 rows + 40 pixels
+      ry += 3;
+      if (rx >= F2_R) { rx -= F2_R; ++ry; }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      float gu = 0.f, gv = 0.f;
+      if (live[j]) {
+        const int a0 = ti[0][0][gy[j]], a1 = ti[0][1][gy[j]], c0 = ti[1][0][gx[j]], c1 = ti[1][1][gx[j]];
+        const float ly = tl[0][gy[j]], lx = tl[1][gx[j]];
+        const float hy0 = 1.f - ly, wx0 = 1.f - lx;
+        const float fu = hy0 * (wx0 * f2[0][a0][c0] + lx * f2[0][a0][c1]) + ly * (wx0 * f2[0][a1][c0] + lx * f2[0][a1][c1]);
+        const float fv = hy0 * (wx0 * f2[1][a0][c0] + lx * f2[1][a0][c1]) + ly * (wx0 * f2[1][a1][c0] + lx * f2[1][a1][c1]);
+        const float tuj = tu[j], tvj = tv[j];
+        float term;
+        if (kind == 0) {
+          const float dot = fu * tuj + fv * tvj;
+          const float nf2 = fu * fu + fv * fv, nt2 = tuj * tuj + tvj * tvj;
+          const float den = fmaxf(sqrtf(nf2 * nt2), 1e-8f);
+          const float c = dot / den;
+          term = 1.0f - c;
+          if (sqrtf(nf2 * nt2) > 1e-8f) {
+            gu = -(tuj / den - c * fu / nf2);
+            gv = -(tvj / den - c * fv / nf2);
+          } else {
+            gu = -(tuj / den);
+            gv = -(tvj / den);
+          }
+        } else {
+          const float du = fu - tuj, dv = fv - tvj;
+          const float sd = sqrtf(du * du + dv * dv + 1e-8f);
+          term = sd;
+          gu = du / sd;
+          gv = dv / sd;
+        }
+        gu *= invn;
+        gv *= invn;
+        if (owned[j]) part += term;
+      }
+      if (store[j]) {
+        g[0][gy[j]][gx[j]] = gu;
+        g[1][gy[j]][gx[j]] = gv;
+      }
+    }
+  }
+  __syncthreads();
+  {                                                                        // one cell per thread
+    const int cyl = tid >> 4, cxl = tid & 15, cy = cy0 + cyl, cx = cx0 + cxl;
+    if (cy < h && cx < w) {
+      float wxs[8];
+      bool vx[8];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {                                        // pixel 4 cx - 2 + t = column 4 cxl + t of g
+        const int c = 4 * cxl + t, x0 = ti[1][0][c], x1 = ti[1][1][c];
+        const float lx = tl[1][c];
+        vx[t] = x0 != 255;
+        wxs[t] = (x0 == cxl + 1 ? 1.f - lx : 0.f) + (x1 == cxl + 1 ? lx : 0.f);
+      }
+      float su = 0.f, sv = 0.f;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int r = 4 * cyl + s, y0 = ti[0][0][r], y1 = ti[0][1][r];
+        if (y0 == 255) continue;
+        const float ly = tl[0][r];
+        const float wy = (y0 == cyl + 1 ? 1.f - ly : 0.f) + (y1 == cyl + 1 ? ly : 0.f);
+        if (wy == 0.f) continue;
+        float ru = 0.f, rv = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+          if (vx[t]) {
+            ru += wxs[t] * g[0][r][4 * cxl + t];
+            rv += wxs[t] * g[1][r][4 * cxl + t];
+          }
+        su += wy * ru;
+        sv += wy * rv;
+      }
+      gflow2[((long)b * 2) * hw + (long)cy * w + cx] = su * flow_scale;
+      gflow2[((long)b * 2 + 1) * hw + (long)cy * w + cx] = sv * flow_scale;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = part;
+  __syncthreads();
+  if (tid == 0) partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) * invn;
+}
+
+extern "C" int ufr_flow2_upsampled_loss_fast(const float* flow2, float flow_scale, const float* target, float* grad_flow2, float* loss,
+                                             int B, int h, int w, int kind, float weight, float* partials, ufr_stream_t stream) {
+  UFR_REQUIRE(flow2 && target && grad_flow2 && loss && partials, "upsampled flow loss (fast): null pointer argument");
+  UFR_REQUIRE(B > 0 && h > 0 && w > 0 && (kind == 0 || kind == 1), "upsampled flow loss (fast): bad argument");
+  const dim3 grid(ufr::ceil_div(w, F2_T), ufr::ceil_div(h, F2_T), B);
+  const long n = (long)grid.x * grid.y * grid.z;
+  if (n > UFR_LOSS_PARTIALS || B > 65535)
+    return ufr::fail(UFR_EUNSUPPORTED, "upsampled flow loss (fast): %ld tiles exceed the %d partial sums of the fixed-order reduction", n,
+                     UFR_LOSS_PARTIALS);
+  hipLaunchKernelGGL(flow2_upsampled_loss_fast_kernel, grid, dim3(256), 0, ufr::as_stream(stream), flow2, flow_scale, target,
+                     grad_flow2, partials, B, h, w, kind, weight);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, ufr::as_stream(stream), partials, (int)n, loss);
+  return ufr::launched("flow2_upsampled_loss_fast_kernel");
+}
+
 namespace ufr {
 void loss_finalize_launch(const float* partials, int n, float* loss, hipStream_t st) {
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, partials, n, loss);

@@ -343,6 +343,144 @@ __global__ __launch_bounds__(512) void flow_head_planes_fwd_mfma(const __bf16* _
   }
 }
 
+// ---- predict_flow* of the starved grids (1/64 .. 1/16): the chunk slices over the grid -------------------------------------
+// MODE 0 above keeps a tile's S chunk slices inside one workgroup, so a 6 x 20 or 24 x 80 grid brings a few dozen workgroups to
+// 256 CUs.  T[p, n] depends on pixel p alone, so here the per-pixel GEMM runs over the FLAT pixel list with no tile and no halo:
+// wave = (16 pixels, slice), grid = (m-tiles / 4, S).  A slice's T (18 floats per pixel) leaves to a float32 buffer
+// Tp [S][B * H * W][18]; flow_head_split_finish gathers it.  Per (pixel, n, slice) the MFMA chain is MODE 0's: the slice's chunks
+// ascending, per chunk the six products in PFM order.
+constexpr int PFS_TS = 18;
+__global__ __launch_bounds__(256) void flow_head_split_gemm(const __bf16* __restrict__ x, long plane_stride, int chunk0, int chunks,
+                                                            const __bf16* __restrict__ wmf, float* __restrict__ Tp, long M, int per) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slice = blockIdx.y;
+  const long m0 = ((long)blockIdx.x * 4 + wave) * 16;
+  if (m0 >= M) return;                                                      // no barrier in this kernel
+  const long p = m0 + (lane & 15);
+  const bool ok = p < M;
+  const __bf16* a = ok ? x + ((long)chunk0 * M + p) * 32 + (lane >> 4) * 8 : reinterpret_cast<const __bf16*>(pf_zero_page);
+  const long astep = ok ? M * 32 : 0;                                       // the zero page does not move
+  const long pstep = ok ? plane_stride : 0;
+  const __bf16* wl = wmf + (lane & 15) * 32 + (lane >> 4) * 8;
+  const int c_lo = slice * per, c_hi = min(chunks, c_lo + per);
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  bf16x8 fa[2][3], fb[2][2][3];                                             // [stage]: this chunk's fragments and the next one's
+  auto fetch = [&](int st, int ch) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      fa[st][pl] = *reinterpret_cast<const bf16x8*>(a + (long)ch * astep + pl * pstep);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) fb[st][nt][pl] = *reinterpret_cast<const bf16x8*>(wl + (((long)ch * 3 + pl) * 2 + nt) * 512);
+    }
+  };
+  auto mma = [&](int st) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int q = 0; q < 6; ++q)
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[st][PFM_A[q]], fb[st][nt][PFM_B[q]], acc[nt], 0, 0, 0);
+  };
+  if (c_lo < c_hi) fetch(0, c_lo);
+  for (int ch = c_lo; ch < c_hi; ch += 2) {
+    if (ch + 1 < c_hi) fetch(1, ch + 1);
+    mma(0);
+    if (ch + 1 < c_hi) {
+      if (ch + 2 < c_hi) fetch(0, ch + 2);
+      mma(1);
+    }
+  }
+  // lane holds D[m = 4 (lane >> 4) + r][n = lane & 15]
+  float* T = Tp + ((long)slice * M + m0 + (lane >> 4) * 4) * PFS_TS;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (m0 + (lane >> 4) * 4 + r < M) {
+      T[r * PFS_TS + (lane & 15)] = acc[0][r];
+      if ((lane & 15) < 2) T[r * PFS_TS + 16 + (lane & 15)] = acc[1][r];
+    }
+}
+
+// The finishing sum of the split form, and upsampled_flow* behind it in the same launch.  Workgroup = 8 x 8 coarse pixels of one
+// image + a halo of 1 (the transposed convolution reads a fine pixel's <= 2 x 2 coarse neighbours; a halo pixel's sum is recomputed).
+// Per coarse pixel ONE running sum in MODE 0's order -- slices ascending, within a slice the nine taps ascending, a tap outside the
+// frame adds 0 -- then the bias; the owned pixels are stored as flow [B, 2, H, W].  With `planes` the 16 x 16 fine pixels under the
+// tile then go through flow_up_planes_fwd's arithmetic, operation for operation, from the sums in LDS.
+constexpr int PFF_T = 8;
+__global__ __launch_bounds__(256) void flow_head_split_finish(const float* __restrict__ Tp, int S, const float* __restrict__ bias,
+                                                              float* __restrict__ flow, const float* __restrict__ w,
+                                                              const float* __restrict__ up_bias, __bf16* __restrict__ planes,
+                                                              long plane_stride, int chunk, int B, int H, int W) {
+  __shared__ float f[2][PFF_T + 2][PFF_T + 2];
+  const int tid = threadIdx.x, b = blockIdx.z, cy0 = blockIdx.y * PFF_T, cx0 = blockIdx.x * PFF_T;
+  const long M = (long)B * H * W, HW = (long)H * W;
+  if (tid < (PFF_T + 2) * (PFF_T + 2)) {
+    const int hy = tid / (PFF_T + 2), hx = tid - hy * (PFF_T + 2), yy = cy0 - 1 + hy, xx = cx0 - 1 + hx;
+    float r0 = 0.f, r1 = 0.f;
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+      int off[9];                                                           // tap k of this pixel inside a slice of one image
+      unsigned inside = 0;                                                  // a tap outside the frame reads the pixel itself and adds 0
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const int y2 = yy + k / 3 - 1, x2 = xx + k % 3 - 1;
+        const bool ok = y2 >= 0 && y2 < H && x2 >= 0 && x2 < W;
+        off[k] = ((ok ? y2 : yy) * W + (ok ? x2 : xx)) * PFS_TS + 2 * k;
+        inside |= ok ? 1u << k : 0u;
+      }
+      for (int sl = 0; sl < S; ++sl) {
+        const float* Ts = Tp + ((long)sl * M + (long)b * HW) * PFS_TS;
+        float2 e[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) e[k] = *reinterpret_cast<const float2*>(Ts + off[k]);   // nine loads in flight, then the sum
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          r0 += (inside >> k & 1u) ? e[k].x : 0.f;
+          r1 += (inside >> k & 1u) ? e[k].y : 0.f;
+        }
+      }
+      r0 += bias[0];
+      r1 += bias[1];
+      if (hy >= 1 && hy <= PFF_T && hx >= 1 && hx <= PFF_T) {
+        flow[((long)b * 2 + 0) * HW + (long)yy * W + xx] = r0;
+        flow[((long)b * 2 + 1) * HW + (long)yy * W + xx] = r1;
+      }
+    }
+    f[0][hy][hx] = r0;
+    f[1][hy][hx] = r1;
+  }
+  if (!planes) return;
+  __syncthreads();
+  const int Ho = 2 * H, Wo = 2 * W;
+  const int Y = 2 * cy0 + (tid >> 4), X = 2 * cx0 + (tid & 15);
+  if (Y >= Ho || X >= Wo) return;
+  float a0 = up_bias ? up_bias[0] : 0.f, a1 = up_bias ? up_bias[1] : 0.f;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int ky = ((Y + 1) & 1) + 2 * t, yy = (Y + 1 - ky) / 2;
+    if (Y + 1 - ky < 0 || yy >= H) continue;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int kx = ((X + 1) & 1) + 2 * u, xx = (X + 1 - kx) / 2;
+      if (X + 1 - kx < 0 || xx >= W) continue;
+#pragma unroll
+      for (int ic = 0; ic < 2; ++ic) {
+        const float v = f[ic][yy - cy0 + 1][xx - cx0 + 1];
+        a0 = fmaf(v, w[((ic * 2 + 0) * 4 + ky) * 4 + kx], a0);
+        a1 = fmaf(v, w[((ic * 2 + 1) * 4 + ky) * 4 + kx], a1);
+      }
+    }
+  }
+  __bf16 s0[3], s1[3];
+  split3(a0, s0[0], s0[1], s0[2]);
+  split3(a1, s1[0], s1[1], s1[2]);
+  const long total = (long)B * Ho * Wo;
+  __bf16* dst = planes + ((long)chunk * total + ((long)b * Ho + Y) * Wo + X) * 32;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    bf16x8 v = {s0[p], s1[p], (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+    const bf16x8 zero = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+    bf16x8* o = reinterpret_cast<bf16x8*>(dst + p * plane_stride);
+    o[0] = v; o[1] = zero; o[2] = zero; o[3] = zero;
+  }
+}
+
 // G[chunk0 + ch][pix][c] (+)= sum_o sum_k gy[b, o, pix - (k - centre)] * weight[o][32*ch + c][k]
 // thread = (pixel, 8-channel group), blockIdx.y = slice of the chunks (independent outputs: no reduction)
 // Optional fused finalisation (round 4): for the chunks [fin_c0, fin_c0 + fin_n) of the tensor -- the segment a deconvolution
@@ -704,6 +842,24 @@ extern "C" int ufr_flow_head_planes_forward(const void* planes, long plane_strid
 }
 
 namespace {
+// What launch_pf_mfma<0> runs on a grid: rows per tile, workgroups, and the chunk slices whose partial sums a pixel adds in
+// ascending order (8 = the one-wave-per-slice form of the small grids).  `starved`: even tiles of 4 rows leave CUs without a
+// workgroup -- the launcher's own test for falling to its smallest tile -- and the split form (flow_head_split_gemm) takes over
+// where the caller asks for it.  The slice count and per = ceil(chunks / S) fix the order of additions, hence the bits.
+struct PfMode0Plan { int TH, blocks, S; bool eight, starved; };
+PfMode0Plan pf_mode0_plan(int B, int H, int W, int chunks) {
+  auto blocks_of = [&](int th) { return (long)B * ufr::ceil_div(H, th) * ufr::ceil_div(W, 32); };
+  PfMode0Plan p;
+  p.TH = blocks_of(8) >= 512 ? 8 : (blocks_of(4) >= 256 ? 4 : 2);
+  p.blocks = (int)blocks_of(p.TH);
+  const int S = (p.blocks >= 512 || chunks < 4) ? 1 : 2;
+  const int mt = ((p.TH + 2) * 34 + 15) / 16;
+  p.eight = mt <= 12 && S == 2 && chunks >= 16 && p.blocks <= 256;
+  p.S = p.eight ? 8 : S;
+  p.starved = blocks_of(4) < 256;
+  return p;
+}
+
 template <int MODE>
 int launch_pf_mfma(const void* planes, long plane_stride, int chunk0, int chunks, const void* wmf, const float* bias, float* out,
                    int out_chunk, int B, int H, int W, hipStream_t st, const char* what) {
@@ -744,6 +900,52 @@ extern "C" int ufr_flow_head_planes_forward_mfma(const void* planes, long plane_
   UFR_REQUIRE_RANGE("flow head (planes, mfma) forward", plane_stride, (long)B * H * W, chunk0, chunks, w_chunks);
   return launch_pf_mfma<0>(planes, plane_stride, chunk0, chunks, wmf, bias, out, 0, B, H, W, ufr::as_stream(stream),
                            "flow_head_planes_fwd_mfma");
+}
+
+extern "C" int ufr_flow_head_split_plan(int B, int H, int W, int chunks, int* slices, int* starved, long* partial_floats) {
+  UFR_REQUIRE(slices && starved && partial_floats, "flow head split plan: null pointer");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && chunks > 0 && chunks <= 48 && (long)B * H * W < (1L << 29), "flow head split plan: bad shape");
+  const PfMode0Plan p = pf_mode0_plan(B, H, W, chunks);
+  *slices = p.S;
+  *starved = p.starved ? 1 : 0;
+  *partial_floats = (long)p.S * B * H * W * PFS_TS;
+  return UFR_OK;
+}
+
+extern "C" int ufr_flow_head_planes_forward_split(const void* planes, long plane_stride, int chunk0, int chunks, const void* wmf,
+                                                  int w_chunks, float* partials, long partial_floats, int slices, int B, int H, int W,
+                                                  ufr_stream_t stream) {
+  UFR_REQUIRE(planes && wmf && partials, "flow head (planes, split) forward: null pointer");
+  UFR_REQUIRE(B > 0 && H > 0 && W > 0 && chunks > 0 && chunks <= 48 && chunk0 >= 0 && (long)B * H * W < (1L << 29),
+              "flow head (planes, split) forward: bad shape");
+  UFR_REQUIRE_RANGE("flow head (planes, split) forward", plane_stride, (long)B * H * W, chunk0, chunks, w_chunks);
+  const PfMode0Plan p = pf_mode0_plan(B, H, W, chunks);
+  UFR_REQUIRE(slices == p.S, "flow head (planes, split) forward: %d chunk slices asked, the unsplit form of this grid adds %d (the sums "
+              "would differ in the last bits)", slices, p.S);
+  const long M = (long)B * H * W;
+  UFR_REQUIRE(partial_floats >= (long)slices * M * PFS_TS, "flow head (planes, split) forward: the partials buffer holds %ld floats, "
+              "%d slices of %ld pixels need %ld", partial_floats, slices, M, (long)slices * M * PFS_TS);
+  const int per = ufr::ceil_div(chunks, slices);
+  flow_head_split_gemm<<<dim3(ufr::ceil_div(M, 64), slices), 256, 0, ufr::as_stream(stream)>>>(
+      static_cast<const __bf16*>(planes), plane_stride, chunk0, chunks, static_cast<const __bf16*>(wmf), partials, M, per);
+  return ufr::launched("flow_head_split_gemm");
+}
+
+extern "C" int ufr_flow_head_split_finish(const float* partials, long partial_floats, int slices, const float* bias, float* flow,
+                                          const float* up_w, const float* up_bias, void* up_planes, long up_plane_stride, int up_chunk,
+                                          int B, int H, int W, ufr_stream_t stream) {
+  UFR_REQUIRE(partials && bias && flow, "flow head split finish: null pointer");
+  UFR_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && slices > 0 && (long)B * H * W < (1L << 27), "flow head split finish: bad shape");
+  UFR_REQUIRE(partial_floats >= (long)slices * B * H * W * PFS_TS, "flow head split finish: the partials buffer holds %ld floats, %d "
+              "slices need %ld", partial_floats, slices, (long)slices * B * H * W * PFS_TS);
+  if (up_planes) {
+    UFR_REQUIRE(up_w && up_chunk >= 0, "flow head split finish: the upsampling needs its weights and a chunk");
+    UFR_REQUIRE(planes_hold(up_plane_stride, (long)B * H * W * 4, up_chunk, 1), "flow head split finish: chunk %d leaves the planes "
+                "operand", up_chunk);
+  }
+  flow_head_split_finish<<<dim3(ufr::ceil_div(W, PFF_T), ufr::ceil_div(H, PFF_T), B), 256, 0, ufr::as_stream(stream)>>>(
+      partials, slices, bias, flow, up_w, up_bias, static_cast<__bf16*>(up_planes), up_plane_stride, up_chunk, B, H, W);
+  return ufr::launched("flow_head_split_finish");
 }
 
 extern "C" int ufr_deconv_flow_tail_backward_mfma(const void* grad_planes, long plane_stride, int chunk0, int chunks, const void* wmf,

@@ -32,6 +32,17 @@ from . import igemm as ig
 _HEADS = ((6, 1024), (5, 1026), (4, 770), (3, 386), (2, 194))
 
 
+def pf_split_plan(B: int, H: int, W: int, chunks: int):
+    """(chunk slices, starved, floats of the partials buffer) of predict_flow on a [B, H, W] grid of `chunks` chunks, from the
+    library (csrc/engine_small.hip `ufr_flow_head_split_plan`): the slices are those of the unsplit launch -- the split form must
+    add the same partial sums in the same order -- and `starved` says that the unsplit launch leaves CUs without a workgroup."""
+    import ctypes
+    slices, starved, floats = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_long(0)
+    L.check(L.lib().ufr_flow_head_split_plan(int(B), int(H), int(W), int(chunks), ctypes.byref(slices), ctypes.byref(starved),
+                                             ctypes.byref(floats)), "predict_flow split plan")
+    return slices.value, bool(starved.value), floats.value
+
+
 def _pack_flow_head(weight: torch.Tensor) -> torch.Tensor:
     """Conv2d(Cin, 2, 3, 1, 1).weight [2,Cin,3,3] -> [chunks][9][2][32] float32 (csrc/engine_small.hip)."""
     cin = weight.shape[1]
@@ -214,6 +225,19 @@ class FlowNetCHeadEngine:
         # upsampled_flowK_to_K-1 writes the last chunk of cat(K-1)
         self.up_dst = {6: (self.cat5, 32), 5: (self.cat4, 24), 4: (self.cat3, 12), 3: (self.cat2, 6)}
         self.up_G = {6: (self.G_cat5, 32), 5: (self.G_cat4, 24), 4: (self.G_cat3, 12), 3: (self.G_cat2, 6)}
+        # predict_flowK on a grid too small to fill the chip with one workgroup per tile: the chunk slices spread over the grid
+        # (csrc/engine_small.hip `flow_head_split_gemm`), the finishing sum runs with upsampled_flowK in one launch.  The rule is
+        # on the workgroup count (ufr_flow_head_split_plan), not on the level; level 2 has no upsampling behind it and stays.
+        self.pf_split, floats = {}, 0
+        for k in (6, 5, 4, 3):
+            src, chunks = self.pf_src[k]
+            slices, starved, n = pf_split_plan(self.B, src.H, src.W, chunks)
+            if starved:
+                self.pf_split[k] = (slices, n)
+                floats = max(floats, n)
+        self.pf_partials = torch.empty(max(floats, 1), dtype=torch.float32, device=self.dev)   # one level at a time uses it
+        self._pf_pending = None                  # the level whose partial sums wait for `_up_forward` to finish them
+        self.pf_ran = {}                         # launch record: level -> "split" | "mfma", what its last forward ran
 
     # ------------------------------------------------------------------------------------------------ conv1-3
     def _with_tail(self, key, plain, args, kw, S, resident=None):
@@ -671,8 +695,21 @@ class FlowNetCHeadEngine:
         return rows
 
     # ------------------------------------------------------------------------------------------------ small launches
-    def _pf_forward(self, k):
+    def _pf_forward(self, k, defer=False):
+        """predict_flowK -> flow[k].  `defer` (the schedules, which run `_up_forward(k)` next): a level on the split form leaves
+        its partial sums for that launch to finish; without it the call leaves a complete flow[k] behind."""
         src, chunks = self.pf_src[k]
+        if k in self.pf_split:
+            slices, n = self.pf_split[k]
+            L.check(L.lib().ufr_flow_head_planes_forward_split(L.ptr(src.t), src.plane_stride, 0, chunks, L.ptr(self.pf_wm[k]),
+                                                               self.pf_wm[k].shape[0], L.ptr(self.pf_partials), n, slices, self.B, src.H,
+                                                               src.W, L.stream()), "predict_flow forward (split)")
+            self.pf_ran[k] = "split"
+            self._pf_pending = k
+            if not defer:
+                self._pf_finish(k, upsample=False)
+            return
+        self.pf_ran[k] = "mfma"
         L.check(L.lib().ufr_flow_head_planes_forward_mfma(L.ptr(src.t), src.plane_stride, 0, chunks, L.ptr(self.pf_wm[k]),
                                                           self.pf_wm[k].shape[0], L.ptr(self.pf_b[k]), L.ptr(self.flow[k]), self.B, src.H, src.W,
                                                           L.stream()), "predict_flow forward (mfma)")
@@ -706,7 +743,21 @@ class FlowNetCHeadEngine:
                                                       self.pf_G[k].chunks, 0, chunks, self.B,
                                                       src.H, src.W, int(accumulate), L.stream()), "predict_flow backward")
 
+    def _pf_finish(self, k, upsample):
+        """The split form's finishing sum -> flow[k]; with `upsample`, upsampled_flowK_to_K-1 from the same launch."""
+        slices, n = self.pf_split[k]
+        f = self.flow[k]
+        dst, chunk = self.up_dst[k] if upsample else (None, 0)
+        L.check(L.lib().ufr_flow_head_split_finish(L.ptr(self.pf_partials), n, slices, L.ptr(self.pf_b[k]), L.ptr(f), L.ptr(self.up_w[k]),
+                                                   L.ptr(self.up_b[k]) if self.up_b[k] is not None else None,
+                                                   L.ptr(dst.t) if upsample else None, dst.plane_stride if upsample else 0, chunk, self.B,
+                                                   f.shape[2], f.shape[3], L.stream()), "predict_flow finish (split)")
+        self._pf_pending = None
+
     def _up_forward(self, k):
+        if self._pf_pending == k:
+            self._pf_finish(k, upsample=True)
+            return
         dst, chunk = self.up_dst[k]
         f = self.flow[k]
         L.check(L.lib().ufr_flow_up_planes_forward(L.ptr(f), L.ptr(self.up_w[k]), L.ptr(self.up_b[k]) if self.up_b[k] is not None else None,
@@ -738,11 +789,11 @@ class FlowNetCHeadEngine:
         self.in31.load_nchw(c3, 0)
         for name in ("conv3_1", "conv4", "conv4_1", "conv5", "conv5_1", "conv6", "conv6_1"):
             self.fwd[name]()
-        self._pf_forward(6)
+        self._pf_forward(6, defer=True)
         for k in (5, 4, 3, 2):
             self._up_forward(k + 1)
             self.fwd[f"deconv{k}"]()
-            self._pf_forward(k)
+            self._pf_forward(k, defer=True)
         return self.flow[2]
 
     def forward_cached(self, band=None, corr_changed: bool = True) -> torch.Tensor:
@@ -798,11 +849,11 @@ class FlowNetCHeadEngine:
         # graph -- they read cat(K+1) and write disjoint chunks of catK -- measured no faster: 5.773 against 5.729 ms in one call,
         # gpurun r4_call23; the same for the small launches of the backward beside deconvK's data gradient, 5.904 against 5.874,
         # r4_call13: the ping-pong igemm holds every CU's LDS, the small launches wait for its tail either way.  One stream.)
-        self._pf_forward(6)
+        self._pf_forward(6, defer=True)
         for k in (5, 4, 3, 2):
             self._up_forward(k + 1)
             self.fwd[f"deconv{k}"]()
-            self._pf_forward(k)
+            self._pf_forward(k, defer=True)
         return self.flow[2]
 
     def backward(self, g_flow2: torch.Tensor, band=None, fused_window: bool = True, skip_unread: bool = True, tail_split: bool = True):
@@ -1007,11 +1058,11 @@ class FlowNetCHeadEngine:
         stage("conv3_1", self.fwd["conv3_1"], lambda v: self.cat3.load_nchw(v, 0))
         for name in ("conv4", "conv4_1", "conv5", "conv5_1", "conv6", "conv6_1"):
             self.fwd[name]()
-        self._pf_forward(6)
+        self._pf_forward(6, defer=True)
         for k in (5, 4, 3, 2):
             self._up_forward(k + 1)
             self.fwd[f"deconv{k}"]()
-            self._pf_forward(k)
+            self._pf_forward(k, defer=True)
         return self.flow[2]
 
 

@@ -428,9 +428,9 @@ class PatchAttackStep:
         # shared patch: loss = mean over the GLOBAL batch; private: every sample its own mean
         weight = (1.0 - self.alpha) * ((1.0 / self.world) if self.shared else float(self.B))
         if flow is None:        # engine head: loss on the x4-upsampled flow2 and its adjoint in one kernel (csrc/attack.hip)
-            L.check(L.lib().ufr_flow2_upsampled_loss(L.ptr(self.eng.flow_out), float(self.eng.flow_scale), L.ptr(self.target),
-                                                     L.ptr(self.g_flow2), L.ptr(self.loss_local), self.B, self.H // 4, self.W // 4,
-                                                     self.kind, weight, L.ptr(self.loss_ws), L.stream()), "upsampled flow loss")
+            L.check(L.lib().ufr_flow2_upsampled_loss_fast(L.ptr(self.eng.flow_out), float(self.eng.flow_scale), L.ptr(self.target),
+                                                          L.ptr(self.g_flow2), L.ptr(self.loss_local), self.B, self.H // 4, self.W // 4,
+                                                          self.kind, weight, L.ptr(self.loss_ws), L.stream()), "upsampled flow loss")
         else:
             if not flow.is_contiguous():
                 flow = flow.contiguous()

@@ -377,13 +377,18 @@ def test_round6_host_switches(monkeypatch):
     monkeypatch.setenv("UFR_RAFT_PRECISION", "fp16")
     with pytest.raises(ValueError):
         net.products()
-    assert ig._PRODUCTS[-1] == 6
+    import threading
+    assert ig.current_products() == 6
     with ig.products(1):
-        assert ig._PRODUCTS[-1] == 1
+        assert ig.current_products() == 1
         with ig.products(3):
-            assert ig._PRODUCTS[-1] == 3
-        assert ig._PRODUCTS[-1] == 1
-    assert ig._PRODUCTS == [6]
+            assert ig.current_products() == 3
+        assert ig.current_products() == 1
+        seen = []
+        t = threading.Thread(target=lambda: seen.append(ig.current_products()))
+        t.start(), t.join()
+        assert seen == [6]                                                 # the stack is per thread: another thread builds at 6
+    assert ig.current_products() == 6 and ig._PRODUCTS.stack == [6]
     with pytest.raises(ValueError):
         ig.products(2)
     wi = ig.conv_forward_weights(torch.randn(64, 32, 3, 3), 1, 1)

@@ -75,6 +75,12 @@ def _pack_flow_tail_mfma(weight2: torch.Tensor) -> torch.Tensor:
     return ig._split3(wn).view(3, chunks, 32, 32).permute(1, 0, 2, 3).contiguous()
 
 
+# Where this engine sizes split-K against another (tile rows, slots) than `igemm.tile_rows_and_slots` says:
+_TILE = {7: (128, 768)}                            # the tap-reuse form as the single-stage tile (kept for bit-stability, unmeasured)
+_WINDOW_TILE = {**_TILE, 4: (128, 768)}            # window prefix: every form but 5 / 6 as that tile (kept for bit-stability, unmeasured)
+_PLAN = dict(min_ktiles=16, tile=_TILE)            # `igemm.plan_splitk` options of every launch of the engine
+
+
 class FlowNetCHeadEngine:
     def __init__(self, net, B: int, H: int, W: int, device):
         if H % 64 or W % 64:
@@ -130,18 +136,12 @@ class FlowNetCHeadEngine:
         return [(name, block[0], lvl) for lvl, stage in enumerate(stem_stages(self.net), 1) for name, block in stage]
 
     def _build_launches(self):
-        net, g, B = self.net, self.grid, self.B
-        plans = []      # (weights, make_launch kwargs without ws) -> sized together for one split-K workspace
+        net, g = self.net, self.grid
+        queue = ig.LaunchQueue(self.dev, **_PLAN)       # sized together for one split-K workspace
 
         def plan(wi, x, in_chunk0, rows, out_hw, **kw):
-            M = B * rows[0] * rows[1]
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
             kw.setdefault("variant", self._variant_for(wi))
-            bm, target = self._tile_rows_and_slots(wi, kw)
-            S = ig.splitk_for(M, wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target)
-            kw["variant"], S = ig.tuned(wi, M, kw, kw["variant"], S, rows=rows)
-            plans.append((wi, x, in_chunk0, rows, out_hw, S, kw))
-            return len(plans) - 1
+            return queue.add(wi, x, in_chunk0, rows, out_hw, **kw)
 
         # 128-column launches: csrc/igemm.hip variant 6 (ping-pong: 256 x 128 tiles, two wave groups of one workgroup per CU half a
         # step apart); UFR_IGEMM_PIPE=5: pipelined 128 x 128, two workgroups per CU; UFR_IGEMM_PIPE=0: the single-stage kernel.
@@ -202,15 +202,13 @@ class FlowNetCHeadEngine:
             bwd["conv_redir"] = plan(cb("conv_redir", 1, 0), self.gz_in31, 0, g[8], g[8], out_f32=self.G_c3a)
         else:                                   # the trunk's input IS conv3's activation: its gradient leaves unmasked
             bwd["conv3_1"] = plan(cb("conv3_1", 1, 1), self.gz_cat3, 0, g[8], g[8], out_f32=self.G_in31)
-        need = max([len(wi.phases) * S * B * rows[0] * rows[1] * wi.Npad for wi, _, _, rows, _, S, _ in plans if S > 1] + [1])
-        self.ws = torch.empty(need, dtype=torch.float32, device=self.dev)
-        launches = [ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
-                    for wi, x, c0, rows, out_hw, S, kw in plans]
-        self.fwd = {k: launches[i] for k, i in fwd.items()}
+        self.ws = queue.build()
+        self.fwd = {k: h.launch for k, h in fwd.items()}
         self.plain = {}                         # (table tag, name): the plain twin of a launch that runs with its last round re-cut
-        self.bwd = {k: self._with_tail(("full", k), launches[i], plans[i][:5], plans[i][6], plans[i][5]) for k, i in bwd.items()}
-        self._plans = {("fwd", k): plans[i] for k, i in fwd.items()}
-        self._plans.update({("bwd", k): plans[i] for k, i in bwd.items()})
+        self.bwd = {k: self._with_tail(("full", k), h.launch, h.args, h.kw, h.S) for k, h in bwd.items()}
+        # (weights, input planes, first chunk, row grid, output grid, split-K factor, make_launch kwargs without ws)
+        self._plans = {("fwd", k): (*h.args, h.S, h.kw) for k, h in fwd.items()}
+        self._plans.update({("bwd", k): (*h.args, h.S, h.kw) for k, h in bwd.items()})
         self._band, self.fwd_band, self.bwd_band = None, {}, {}
         self.bwd_band_wide, self.bwd_rest, self._band_plans, self._pf_band, self._split_w = {}, {}, {}, {}, {}
         # 2-channel layers
@@ -263,20 +261,6 @@ class FlowNetCHeadEngine:
     def _variant_for(self, wi):
         """The igemm form of a launch: the 128-column forms as `UFR_IGEMM_PIPE` says, 64-column launches single-stage."""
         return self._pipe_variant if wi.Npad % 128 == 0 else 2
-
-    @staticmethod
-    def _tile_rows_and_slots(wi, kw):
-        """(tile rows, resident workgroups on the chip) of the kernel a launch runs on: what split-K is sized against."""
-        v = kw.get("variant", 0)
-        if wi.Npad % 128:
-            return 128, 768                    # single-stage 128 x 64 tiles, three workgroups per CU
-        if v == 4:
-            return 64, 1024                    # 64 x 128 tiles, four workgroups per CU
-        if v == 5:
-            return 128, 512                    # register-held fragments: two workgroups per CU
-        if v == 6:
-            return 256, 256                    # ping-pong: one 256-row workgroup per CU
-        return 128, 768
 
     def _build_prefix(self):
         """Full-frame prefix for both frames of every pair (models/FlowNetC.py:100-119; the stages of Robust FlowNetC,
@@ -417,36 +401,27 @@ class FlowNetCHeadEngine:
         G_p = ig.GradSum(B2, h2 + 3, w2 + 2, 1, dev)
         G_gw2 = ig.GradSum(B2, h4, w4, 4, dev)       # the conv2 tap's window gradient (first frames; second frames stay 0)
         grid = lambda i: (wh >> layers[i][2], ww >> layers[i][2])
-        plans, names = [], []
+        queue, names = ig.LaunchQueue(dev, tune=False, **dict(_PLAN, tile=_WINDOW_TILE)), []
+        plan = lambda wi, x, rows, out_hw, **kw: queue.add(wi, x, 0, rows, out_hw, **{"variant": self._variant_for(wi), **kw})
         # (the window's forward convolutions: 64 x 128 tiles measured 1.3x faster than 128 x 128 at the same split,
         # 0.047 vs 0.055 ms)
         for i in range(1, n):
             name, conv, _ = layers[i]
-            plans.append((ig.conv_forward_weights(conv.weight, conv.stride[0], conv.padding[0]), acts[i - 1], grid(i), grid(i),
-                          dict(out_planes=acts[i], bias=self._bias(conv), variant=4)))
+            plan(ig.conv_forward_weights(conv.weight, conv.stride[0], conv.padding[0]), acts[i - 1], grid(i), grid(i),
+                 out_planes=acts[i], bias=self._bias(conv), variant=4)
             names.append(name)
         # data gradients, last layer first: x LeakyReLU'(the layer below) -> its gradient planes; where the conv2 tap's output
         # is reached, the skip connection's gradient is added in the same epilogue
         for i in range(n - 1, 0, -1):
             name, conv, _ = layers[i]
             kw = dict(add=G_gw2, mask=acts[i - 1], out_planes=gz[i - 1]) if i - 1 == tap2 else dict(out_planes=gz[i - 1], mask=acts[i - 1])
-            plans.append((ig.conv_backward_weights(conv.weight, conv.stride[0], conv.padding[0]), gz[i], grid(i), grid(i - 1), kw))
+            plan(ig.conv_backward_weights(conv.weight, conv.stride[0], conv.padding[0]), gz[i], grid(i), grid(i - 1), **kw)
             names.append(name + "_bwd")
         # conv1's data gradient with respect to the packed planes (the unpacking follows)
-        plans.append((ig.conv1_packed_backward_weights(layers[0][1].weight), gz[0], (h2 + 3, w2 + 2), (h2 + 3, w2 + 2),
-                      dict(out_f32=G_p)))
+        plan(ig.conv1_packed_backward_weights(layers[0][1].weight), gz[0], (h2 + 3, w2 + 2), (h2 + 3, w2 + 2), out_f32=G_p)
         names.append(layers[0][0] + "_bwd")
-        sized = []
-        for wi, x, rows, out_hw, kw in plans:
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            kw.setdefault("variant", self._variant_for(wi))
-            bm, target = self._tile_rows_and_slots(wi, kw) if kw.get("variant") in (5, 6) else (128, 768)
-            sized.append(ig.splitk_for(B2 * rows[0] * rows[1], wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target))
-        need = max([len(wi.phases) * S * B2 * rows[0] * rows[1] * wi.Npad for (wi, _, rows, _, _), S in zip(plans, sized) if S > 1] + [1])
-        ws = torch.empty(need, **f32)
-        launches = [ig.make_launch(wi, x, 0, rows, out_hw, splitk=S, ws=ws if S > 1 else None, **kw)
-                    for (wi, x, rows, out_hw, kw), S in zip(plans, sized)]
-        chain = [(name, launch, p[0]) for name, launch, p in zip(names, launches, plans)]
+        ws = queue.build()
+        chain = [(name, h.launch, h.wi) for name, h in zip(names, queue.handles)]
         P = dict(hw=(wh, ww), c1=acts[0], c2=acts[tap2], c3=acts[-1], gz_c3=gz[-1], gz_c2=gz[tap2], G_gw2=G_gw2, ws=ws,
                  acts=acts, gz=gz, fwd=chain[:n - 1], bwd=chain[n - 1:],
                  G_p=G_p, gxw=torch.zeros(B2, 3, wh, ww, **f32),
@@ -558,16 +533,10 @@ class FlowNetCHeadEngine:
             extra = dict(row_band=(origin, 8, ls_rows))
             if ls_in is not None:
                 extra["in_band"] = (origin, 8, ls_in, band.width // ls_in)
-            M = self.B * rows_b[0] * rows_b[1]
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            bm, target = self._tile_rows_and_slots(wi, kw)
-            Sb = ig.splitk_for(M, wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target)
-            if len(wi.phases) * Sb * M * wi.Npad > self.ws.numel():
-                Sb = 1
-            launch = ig.make_launch(wi, x, c0, rows_b, out_hw, splitk=Sb, ws=self.ws if Sb > 1 else None, **kw, **extra)
+            h = ig.planned_launch(wi, x, c0, rows_b, out_hw, ws=self.ws, options=dict(_PLAN, tune=False), **kw, **extra)   # (the plan's form)
             if kind == "bwd":
-                launch = self._with_tail(("band", name), launch, (wi, x, c0, rows_b, out_hw), dict(kw, **extra), Sb, resident)
-            return launch
+                return self._with_tail(("band", name), h.launch, h.args, h.kw, h.S, resident)
+            return h.launch
 
         for name, (ls_rows, _) in self._FWD_BAND.items():
             if ("fwd", name) in self._plans:
@@ -588,20 +557,11 @@ class FlowNetCHeadEngine:
         deconv4's segment, read in full by the next deconvolution's gradient) on every row; (b) conv3_1 / conv_redir on the
         correlation-reach band (`band.corr_width` pixels from `band.win[:, 2]`: what the window's correlation adjoint reads), their
         input still masked to the wide band, on which gz_cat3 exists.  The wide forms stay in `bwd_band_wide`."""
-        B = self.B
-
         def planned(name, wi, x, c0, rows, out_hw, kw):
-            M = B * rows[0] * rows[1]
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
             kw.setdefault("variant", self._variant_for(wi))       # (a narrower band of a planned layer keeps that plan's form)
-            bm, target = self._tile_rows_and_slots(wi, kw)
-            S = ig.splitk_for(M, wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target)
-            kw["variant"], S = ig.tuned(wi, M, kw, kw["variant"], S, rows=rows)
-            if len(wi.phases) * S * M * wi.Npad > self.ws.numel():
-                S = 1
-            self._band_plans[name] = (wi, x, c0, rows, out_hw, kw)
-            launch = ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
-            return self._with_tail(("rest" if name.endswith(" rest") else "band", name), launch, (wi, x, c0, rows, out_hw), kw, S,
+            h = ig.planned_launch(wi, x, c0, rows, out_hw, ws=self.ws, options=_PLAN, **kw)
+            self._band_plans[name] = (*h.args, h.kw)
+            return self._with_tail(("rest" if name.endswith(" rest") else "band", name), h.launch, h.args, h.kw, h.S,
                                    getattr(band, "tail_resident", None))
 
         for k, (lead, ls) in self._SPLIT_DECONV.items():

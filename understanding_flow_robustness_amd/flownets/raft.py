@@ -435,7 +435,7 @@ class RAFT(nn.Module):
         from ..plane_graph import graph_for, run, stem_graph
         b, _, h, w = x.shape
         # (the launches bake the products of their arithmetic in, like the BasicEncoder's engine: the key carries them)
-        g = graph_for(self, ("context_stem", b, h, w, str(x.device), ig._PRODUCTS[-1]),
+        g = graph_for(self, ("context_stem", b, h, w, str(x.device), ig.current_products()),
                       lambda: stem_graph(self.fnet, b, h, w, 3, x.device, head=self.conv_redir))
         c3, ctx = run(g, x)
         return c3[:n], c3[n:], ctx[:n]

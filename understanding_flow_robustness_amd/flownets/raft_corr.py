@@ -110,6 +110,9 @@ def _all_pairs_planes(device, H, W, chunks):
 
 
 _ALL_PAIRS_ADJOINT = L.LruDict(4)
+# `igemm.plan_splitk` options of the adjoint products: one-tap launches on the ping-pong form, split-K against its tile whatever
+# the tuning table makes of the form; each launch owns its workspace
+_ADJOINT_PLAN = dict(min_ktiles=4, tile=(256, 256), phases=1)
 
 
 def _all_pairs_adjoint(fmap1, fmap2, g, scale, needs):
@@ -124,10 +127,8 @@ def _all_pairs_adjoint(fmap1, fmap2, g, scale, needs):
                                             Wf=ig.Planes(1, 1, C_, HW // 32, dev),           # a feature map [C, HW] as the weights
                                             out=ig.GradSum(1, H, W, C_ // 32, dev))
         wi = ig.planes_as_weights(st["Wf"])
-        S = ig.splitk_for(HW, wi.Npad, wi.KC, 1, bm=256, target=256, min_ktiles=4)
-        wi_variant, S = ig.tuned(wi, HW, dict(out_f32=st["out"]), 6, S)
-        st["ws"] = torch.empty(max(1, S * HW * wi.Npad), dtype=torch.float32, device=dev) if S > 1 else None
-        st["launch"] = ig.make_launch(wi, st["A"], 0, (H, W), (H, W), out_f32=st["out"], splitk=S, ws=st["ws"], variant=wi_variant)
+        st["launch"] = ig.planned_launch(wi, st["A"], 0, (H, W), (H, W), by_grid=False, options=dict(_ADJOINT_PLAN, ktiles=wi.KC),
+                                         out_f32=st["out"], variant=6).launch
     A, Wf, out, launch = st["A"], st["Wf"], st["out"], st["launch"]
     f1, f2 = fmap1.detach().contiguous().view(B, C_, HW), fmap2.detach().contiguous().view(B, C_, HW)
     g1 = torch.empty_like(fmap1) if needs[0] else None
@@ -196,12 +197,7 @@ def alt_dense_adjoint(f1, f2s, g_vols, scale):
             for name, A, W_, out, rows, extra in (("p1", A1, Wf, st["out1"], (H1, W1), dict(add=st["out1"]) if l else {}),
                                                   ("p2", A2, st["W1"], out2, (Hl, Wl), {})):
                 wi = ig.planes_as_weights(W_)
-                M = rows[0] * rows[1]
-                kw = dict(out_f32=out, **extra)
-                S = ig.splitk_for(M, wi.Npad, wi.KC, 1, bm=256, target=256, min_ktiles=4)
-                variant, S = ig.tuned(wi, M, kw, 6, S, rows=rows)
-                ws = torch.empty(max(1, S * M * wi.Npad), dtype=torch.float32, device=dev) if S > 1 else None
-                lv[name] = ig.make_launch(wi, A, 0, rows, rows, splitk=S, ws=ws, variant=variant, **kw)
+                lv[name] = ig.planned_launch(wi, A, 0, rows, rows, options=dict(_ADJOINT_PLAN, ktiles=wi.KC), out_f32=out, variant=6, **extra).launch
             st["levels"].append(lv)
         _ALT_DENSE[key] = st
     g_f1 = torch.empty_like(f1)

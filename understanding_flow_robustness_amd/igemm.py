@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 
 import os
+import threading
 
 import torch
 
@@ -345,8 +346,19 @@ _TUNING = None
 # one kernel boundary.  It stays an opt-in: UFR_IGEMM_FUSE_REDUCE=1, or `fuse_reduce=True` per launch.
 FUSE_REDUCE = os.environ.get("UFR_IGEMM_FUSE_REDUCE", "0") == "1"
 # Products per float32 product of the launches being built: 6 everywhere; RAFT's engines build theirs inside `with products(1):` when
-# the caller opted into reduced precision (flownets/raft.py `raft_precision`).
-_PRODUCTS = [6]
+# the caller opted into reduced precision (flownets/raft.py `raft_precision`).  The stack is per thread (like `_lib.static_handoff`): a
+# thread that builds engines while another is inside `with products(1)` gets 6.
+class _ProductsStack(threading.local):
+    def __init__(self):
+        self.stack = [6]
+
+
+_PRODUCTS = _ProductsStack()
+
+
+def current_products() -> int:
+    """Products per float32 product of a launch made now, in this thread."""
+    return _PRODUCTS.stack[-1]
 
 
 class products:
@@ -357,10 +369,10 @@ class products:
         self.n = n
 
     def __enter__(self):
-        _PRODUCTS.append(self.n)
+        _PRODUCTS.stack.append(self.n)
 
     def __exit__(self, *exc):
-        _PRODUCTS.pop()
+        _PRODUCTS.stack.pop()
 
 
 RECORD = None            # a list while tools/sweep_engine_launches.py builds a step: every make_launch() appends its arguments
@@ -511,7 +523,7 @@ def make_launch(wi: WeightImage, x: Planes, in_chunk0: int, rows_hw, out_hw, *, 
         tickets = torch.zeros(d.nphase * (-(-(x.B * d.Hr * d.Wr) // 64)) * (wi.Npad // 64), dtype=torch.int32, device=x.t.device)
         d.tickets = tickets.data_ptr()
         keep.append(tickets)
-    d.products = int(_PRODUCTS[-1] if products is None else products)
+    d.products = int(current_products() if products is None else products)
     d.k_order = int(wi.k_order)
     d.variant = int(variant)               # 0 / 2 = single-stage tiles, 4 = 64 x 128, 5 = pipelined, 6 = ping-pong (csrc/igemm.hip)
     if balance:
@@ -563,6 +575,105 @@ def splitk_for(M: int, Npad: int, ktiles: int, phases: int = 1, target: int = 76
     while tiles * s * 2 <= target and ktiles // (s * 2) >= min_ktiles and s < 32:
         s *= 2
     return s
+
+
+# ---------------------------------------------------------------------------------------------------- launch planner
+_TILE = {4: (64, 1024), 5: (128, 512), 6: (256, 256), 7: (256, 256)}
+
+
+def tile_rows_and_slots(Npad: int, variant: int, override=None):
+    """(tile rows, resident workgroups on the chip) of the kernel form a launch runs on: what `splitk_for` sizes split-K against
+    (`bm`, `target`).  Tile rows = output rows one workgroup covers; resident workgroups = how many the 256 CUs hold at once.
+    128-column launches: 64 x 128 tiles, four per CU (4); register-held fragments, two per CU (5); ping-pong and its tap-reuse form,
+    one 256-row workgroup per CU (6, 7); anything else the single-stage 128-row tile, three per CU.  64-column launches: 256 x 64
+    tap-reuse tiles (7), else the single-stage 128 x 64 tile.  `override` {variant: (rows, slots)} goes first: an engine's deviation."""
+    if override and variant in override:
+        return override[variant]
+    if Npad % 128:
+        return (256, 256) if variant == 7 else (128, 768)
+    return _TILE.get(variant, (128, 768))
+
+
+def plan_splitk(wi: "WeightImage", M: int, kw: dict, *, min_ktiles: int, rows=None, tile=None, tune: bool = True, phases=None,
+                ktiles=None):
+    """(variant, split-K factor) of one launch of `wi` over M rows whose make_launch keywords are `kw` (with the engine's default
+    `variant`): the rule of thumb (`splitk_for` against the tile of that form), then the tuning table unless `tune=False`.
+    rows = (Hr, Wr): the table's long form is looked up first (None: the short form only).  tile: None = `tile_rows_and_slots`, a dict
+    = its `override`, a pair = that (tile rows, slots) whatever the form.  phases: what `splitk_for` counts as phases (None: the
+    weight image's).  ktiles: the reduction's K tiles as one number instead of the per-phase list (None: taps x chunks per phase)."""
+    variant = kw.get("variant", 0)
+    bm, target = tile if isinstance(tile, tuple) else tile_rows_and_slots(wi.Npad, variant, tile)
+    pk = [len(t) * wi.KC for _, _, t in wi.phases] if ktiles is None else None
+    S = splitk_for(M, wi.Npad, max(pk) if pk else ktiles, len(wi.phases) if phases is None else phases, phase_ktiles=pk, bm=bm,
+                   target=target, min_ktiles=min_ktiles)
+    return tuned(wi, M, kw, variant, S, rows=rows) if tune else (variant, S)
+
+
+class PlannedLaunch:
+    """A launch queued on a `LaunchQueue`: callable once the queue is built.  `kw` = its make_launch keywords without `splitk` /
+    `ws` (an engine may edit them until the launch is planned); `S`, `launch` = what planning / building gave it."""
+    S = launch = None
+
+    def __init__(self, wi, x, in_chunk0, rows, out_hw, pool, kw):
+        self.wi, self.x, self.in_chunk0, self.rows, self.out_hw = wi, x, in_chunk0, rows, out_hw
+        self.M = x.B * rows[0] * rows[1]
+        self.pool, self.kw = pool, kw
+
+    @property
+    def args(self):
+        return self.wi, self.x, self.in_chunk0, self.rows, self.out_hw
+
+    def ws_floats(self) -> int:
+        return len(self.wi.phases) * self.S * self.M * self.wi.Npad
+
+    def __call__(self):
+        self.launch()
+
+
+class LaunchQueue:
+    """An engine's igemm launches, planned one by one and built together over one float32 split-K workspace (per `pool`: launches
+    that run side by side on two streams must not share slabs).  The keywords of the constructor are `plan_splitk` options for
+    every launch; `by_grid=False` keeps the launch's row grid out of the tuning-table lookup."""
+
+    def __init__(self, device, *, by_grid: bool = True, **options):
+        self.device, self.by_grid, self.options = torch.device(device), by_grid, options
+        self.handles, self.ws = [], {}
+
+    def add(self, wi, x, in_chunk0, rows, out_hw, *, pool=None, **kw) -> PlannedLaunch:
+        """Queue make_launch(wi, x, in_chunk0, rows, out_hw, **kw); `kw` carries the launch's default `variant`."""
+        h = PlannedLaunch(wi, x, in_chunk0, rows, out_hw, pool, kw)
+        self.handles.append(h)
+        return h
+
+    def plan(self):
+        """(variant, S) of every launch queued since the last call, from its keywords as they are now."""
+        for h in self.handles:
+            if h.S is None:
+                h.kw["variant"], h.S = plan_splitk(h.wi, h.M, h.kw, rows=h.rows if self.by_grid else None, **self.options)
+        return self
+
+    def build(self, ws: torch.Tensor | None = None):
+        """make_launch for every queued launch, in queue order.  ws=None: one workspace per pool, sized for the pool's largest split
+        launch (never less than one float), on the queue's device; returns the default pool's.  A given `ws` is used as it is, and a
+        launch whose slabs do not fit runs unsplit."""
+        self.plan()
+        for h in self.handles:
+            if ws is not None and h.S > 1 and h.ws_floats() > ws.numel():
+                h.S = 1
+        for pool in dict.fromkeys(h.pool for h in self.handles):
+            need = max([h.ws_floats() for h in self.handles if h.pool == pool and h.S > 1] + [1])
+            self.ws[pool] = ws if ws is not None else torch.empty(need, dtype=torch.float32, device=self.device)
+        for h in self.handles:
+            h.launch = make_launch(*h.args, splitk=h.S, ws=self.ws[h.pool] if h.S > 1 else None, **h.kw)
+        return self.ws.get(None)
+
+
+def planned_launch(wi, x, in_chunk0, rows, out_hw, *, ws=None, by_grid: bool = True, options: dict, **kw) -> PlannedLaunch:
+    """One launch planned and built on its own: over the given workspace (unsplit when it does not fit) or one of its own."""
+    q = LaunchQueue(x.t.device, by_grid=by_grid, **options)
+    h = q.add(wi, x, in_chunk0, rows, out_hw, **kw)
+    q.build(ws)
+    return h
 
 
 # ---------------------------------------------------------------------------------------------------- weight gradient

@@ -50,7 +50,7 @@ class PlaneGraph:
         self.B, self.dev = int(B), torch.device(device)
         self.bufs: dict[str, _Buf] = {}
         self.ops = []                      # forward order
-        self._plans = []
+        self._plans, self._queue = [], ig.LaunchQueue(self.dev, min_ktiles=4)
         self.flows: dict[str, torch.Tensor] = {}
         self.g_flows: dict[str, torch.Tensor] = {}
         self.inputs, self.outputs, self.tensor_outputs = [], [], []
@@ -62,9 +62,9 @@ class PlaneGraph:
         return self.bufs[name]
 
     def _launch(self, wi, x, in_chunk0, rows, out_hw, **kw):
-        holder = _Deferred()
         kw.setdefault("variant", 6 if wi.Npad % 128 == 0 else 7)
-        self._plans.append((holder, wi, x, in_chunk0, rows, out_hw, kw))
+        holder = self._queue.add(wi, x, in_chunk0, rows, out_hw, **kw)       # (planned at build(): its keywords still change)
+        self._plans.append((holder, wi, x, in_chunk0, rows, out_hw, holder.kw))
         return holder
 
     def input(self, buf, channels, chunk0=0):
@@ -248,7 +248,6 @@ class PlaneGraph:
         return fills, zero_flows
 
     def build(self):
-        B = self.B
         if __import__("os").environ.get("UFR_GRAPH_FUSE_FINALIZE", "1") != "0":
             self._fuse_single_reader_segments()
         if __import__("os").environ.get("UFR_GRAPH_ZERO_ARENA", "0") == "1":          # round 4's form: one fill of everything
@@ -274,18 +273,7 @@ class PlaneGraph:
             off += r64(n)
         # what a backward still has to zero before its first launch (None: everything, as one fill)
         self._zero_list = None if fills is None else ([b.grad.t[c0:c1] for b, c0, c1 in fills] + [self.g_flows[k] for k in zero_flows])
-        sized = []
-        for holder, wi, x, c0, rows, out_hw, kw in self._plans:
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            bm, target = (256, 256) if kw["variant"] in (6, 7) else (128, 768)
-            S = ig.splitk_for(B * rows[0] * rows[1], wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target, min_ktiles=4)
-            kw["variant"], S = ig.tuned(wi, B * rows[0] * rows[1], kw, kw["variant"], S, rows=rows)
-            sized.append(S)
-        need = max([len(p[1].phases) * S * B * p[4][0] * p[4][1] * p[1].Npad for p, S in zip(self._plans, sized) if S > 1] + [1])
-        self.ws = torch.empty(need, dtype=torch.float32, device=self.dev)
-        for (holder, wi, x, c0, rows, out_hw, kw), S in zip(self._plans, sized):
-            holder.launch = ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
-            holder.wi = wi
+        self.ws = self._queue.build()
         return self
 
     def launch_table(self):
@@ -372,13 +360,6 @@ class PlaneGraph:
                 b.grad.to_nchw(spec["C"], spec["chunk0"], slope=1.0, out=spec["g"])
             outs.append(spec["g"])
         return outs
-
-
-class _Deferred:
-    launch = None
-
-    def __call__(self):
-        self.launch()
 
 
 class _GraphFunction(torch.autograd.Function):

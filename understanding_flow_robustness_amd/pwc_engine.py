@@ -82,13 +82,14 @@ class _PyramidPrefix:
         names = [nm for _, _, first, second, third in net._PYRAMID[:2] for nm in ("conv" + first, "conv" + second, "conv" + third)]
         acts = [self.x, self.a1, self.aa1, self.b1, self.a2, self.aa2, self.f2]
         lv = [0, 1, 1, 1, 2, 2, 2]
-        plans = []
+        queue, planned = ig.LaunchQueue(dev, min_ktiles=4, tune=False), {}
+        plan = lambda wi, x, rows, out_hw, **kw: queue.add(wi, x, 0, rows, out_hw, variant=eng._variant_for(wi), **kw)
         for i, nm in enumerate(names):
             conv = getattr(net, nm)[0]
             wgt = conv.weight.detach().flip(1) if i == 0 else conv.weight.detach()
             stride = 2 if i in (0, 3) else 1
-            plans.append(("fwd", i, ig.conv_forward_weights(wgt, stride, 1), acts[i], dims[lv[i + 1]], dims[lv[i + 1]],
-                          dict(out_planes=acts[i + 1], bias=conv.bias.detach().float().contiguous())))
+            planned["fwd", i] = plan(ig.conv_forward_weights(wgt, stride, 1), acts[i], dims[lv[i + 1]], dims[lv[i + 1]],
+                                     out_planes=acts[i + 1], bias=conv.bias.detach().float().contiguous())
         if backward:
             self.gz = [None] + [P(lv[i]) for i in range(1, 7)]          # gradient planes of the six outputs
             self.G_x = ig.GradSum(n, h, w, 1, dev)
@@ -99,7 +100,7 @@ class _PyramidPrefix:
                 wgt = conv.weight.detach().flip(1) if i == 0 else conv.weight.detach()
                 stride = 2 if i in (0, 3) else 1
                 kw = dict(out_f32=self.G_x) if i == 0 else dict(out_planes=self.gz[i], mask=acts[i])
-                plans.append(("bwd", i, ig.conv_backward_weights(wgt, stride, 1), self.gz[i + 1], dims[lv[i + 1]], dims[lv[i]], kw))
+                planned["bwd", i] = plan(ig.conv_backward_weights(wgt, stride, 1), self.gz[i + 1], dims[lv[i + 1]], dims[lv[i]], **kw)
         conv1a = getattr(net, names[0])[0]
         self._w1a = conv1a.weight.detach().flip(1).float().contiguous()              # [16, 3 (BGR order folded), 3, 3]
         self._b1a = conv1a.bias.detach().float().contiguous()
@@ -112,20 +113,11 @@ class _PyramidPrefix:
             if direct and tuple(c16.weight.shape) == (16, 16, 3, 3):
                 self._direct16[i] = (c16.weight.detach().float().permute(1, 2, 3, 0).reshape(16, 9, 16).contiguous(),
                                      c16.bias.detach().float().contiguous())
-        sized = []
-        for kind, i, wi, x, rows, out_hw, kw in plans:
-            kw["variant"] = eng._variant_for(wi)
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            bm, target = eng._tile(wi, kw["variant"])
-            sized.append(ig.splitk_for(n * rows[0] * rows[1], wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target,
-                                       min_ktiles=4))
-        need = max([len(p[2].phases) * S * n * p[4][0] * p[4][1] * p[2].Npad for p, S in zip(plans, sized) if S > 1] + [1])
-        self.ws = torch.empty(need, dtype=torch.float32, device=dev)
+        self.ws = queue.build()
         self.fwd, self.bwd, self.wi = {}, {}, {}
-        for (kind, i, wi, x, rows, out_hw, kw), S in zip(plans, sized):
-            launch = ig.make_launch(wi, x, 0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
-            (self.fwd if kind == "fwd" else self.bwd)[i] = launch
-            self.wi[(kind, i)] = wi
+        for (kind, i), p in planned.items():
+            (self.fwd if kind == "fwd" else self.bwd)[i] = p.launch
+            self.wi[(kind, i)] = p.wi
 
     @torch.no_grad()
     def forward(self, frames: torch.Tensor) -> ig.Planes:
@@ -181,29 +173,18 @@ class PwcHeadEngine:
         of taps is staged once (csrc/igemm.hip variant 7; launches it does not cover run the single-stage 128 x 64 tile)."""
         return self._pipe_variant if wi.Npad % 128 == 0 else self._narrow_variant
 
-    def _tile(self, wi, variant):
-        if wi.Npad % 128:
-            return (256, 256) if variant == 7 else (128, 768)
-        return {4: (64, 1024), 5: (128, 512), 6: (256, 256), 7: (256, 256)}.get(variant, (128, 768))
-
     def _build(self):
         net, B, dev, g = self.net, self.B, self.dev, self.grid
         f32 = dict(dtype=torch.float32, device=dev)
         P = lambda n, k, chunks: ig.Planes(n, g[k][0], g[k][1], chunks, dev)
         G = lambda n, k, chunks: ig.GradSum(n, g[k][0], g[k][1], chunks, dev)
         Z = lambda n, c, k: torch.zeros(n, c, *g[k], **f32)
-        plans, self.fwd, self.bwd = [], {}, {}
+        queue, planned, self.fwd, self.bwd = ig.LaunchQueue(dev, min_ktiles=4), {}, {}, {}
 
         def plan(key, kind, wi, x, in_chunk0, rows_k, out_k, **kw):
             """Queue a launch over the row grid of level rows_k whose output lives on level out_k."""
-            n = x.B
             kw.setdefault("variant", self._variant_for(wi))
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            bm, target = self._tile(wi, kw["variant"])
-            S = ig.splitk_for(n * g[rows_k][0] * g[rows_k][1], wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target,
-                              min_ktiles=4)
-            kw["variant"], S = ig.tuned(wi, n * g[rows_k][0] * g[rows_k][1], kw, kw["variant"], S, rows=g[rows_k])
-            plans.append((key, kind, wi, x, in_chunk0, g[rows_k], g[out_k], S, kw))
+            planned[kind, key] = queue.add(wi, x, in_chunk0, g[rows_k], g[out_k], **kw)
 
         bias = lambda name: self._conv(name).bias.detach().float().contiguous()
         # ---- pyramid levels 3-6 on both frames (2B images) ---------------------------------------------------------------
@@ -357,13 +338,11 @@ class PwcHeadEngine:
         self._prefix, self._wprefixes, self._wprefix = None, {}, None
         self.flow_out, self.flow_scale = self.flow2, 20.0             # what the step's fused loss kernel reads (PWCNet.py:367)
         # ---- one split-K workspace for every launch ------------------------------------------------------------------------
-        need = max([len(wi.phases) * S * x.B * rows[0] * rows[1] * wi.Npad for _, _, wi, x, _, rows, _, S, _ in plans if S > 1] + [1])
-        self.ws = torch.empty(need, **f32)
+        self.ws = queue.build()
         self._plans = {}
-        for key, kind, wi, x, c0, rows, out_hw, S, kw in plans:
-            launch = ig.make_launch(wi, x, c0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
-            (self.fwd if kind == "fwd" else self.bwd)[key] = launch
-            self._plans[(kind, key)] = wi
+        for (kind, key), h in planned.items():
+            (self.fwd if kind == "fwd" else self.bwd)[key] = h.launch
+            self._plans[(kind, key)] = h.wi
         self._corr_p = correlation._params(1, 1, 9, 9, 0, 0, 1, 1, 1, 1, 1, 1)              # PWCNet.py:42-50
 
     def launch_table(self):

@@ -108,14 +108,14 @@ class RaftEncoderEngine:
         if enc.norm_fn not in ("instance", "batch"):
             raise NotImplementedError("RAFT encoder engine: instance (fnet) or batch (cnet, eval) normalisation")
         self.generation = 0
-        self._plans = []
+        self._plans, self._queue = [], ig.LaunchQueue(self.dev, min_ktiles=4)
         self._build()
 
     def launch(self, wi, x, rows, out_hw, **kw):
         """Deferred igemm launch (one split-K workspace for the whole encoder is sized at the end of _build)."""
         kw.setdefault("variant", 6 if wi.Npad % 128 == 0 else 7)
-        holder = _Deferred()
-        self._plans.append((holder, wi, x, rows, out_hw, kw))
+        holder = self._queue.add(wi, x, 0, rows, out_hw, **kw)
+        self._plans.append((holder, wi, x, rows, out_hw, holder.kw))
         return holder
 
     def _build(self):
@@ -162,19 +162,7 @@ class RaftEncoderEngine:
         self.g_image = torch.zeros(n, 3, self.H, self.W, dtype=torch.float32, device=dev)
         self.G_a0 = self.blocks[0]["G_x"]
         # ---- one split-K workspace, one float64 workspace for the statistics
-        sized = []
-        for holder, wi, xin, rows, out_hw, kw in self._plans:
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            v = kw["variant"]
-            bm, target = (256, 256) if v in (6, 7) else (128, 768)
-            S = ig.splitk_for(n * rows[0] * rows[1], wi.Npad, max(pk), len(wi.phases), phase_ktiles=pk, bm=bm, target=target, min_ktiles=4)
-            kw["variant"], S = ig.tuned(wi, n * rows[0] * rows[1], kw, v, S, rows=rows)
-            sized.append(S)
-        need = max([len(p[1].phases) * S * n * p[3][0] * p[3][1] * p[1].Npad for p, S in zip(self._plans, sized) if S > 1] + [1])
-        self.ws = torch.empty(need, dtype=torch.float32, device=dev)
-        for (holder, wi, xin, rows, out_hw, kw), S in zip(self._plans, sized):
-            holder.launch = ig.make_launch(wi, xin, 0, rows, out_hw, splitk=S, ws=self.ws if S > 1 else None, **kw)
-            holder.wi = wi
+        self.ws = self._queue.build()
         self.ws_d = torch.empty(L.lib().ufr_cm_norm_workspace_doubles(H2 * W2, n, 4), dtype=torch.float64, device=dev)
 
     def launch_table(self):
@@ -225,14 +213,6 @@ class RaftEncoderEngine:
         return self.g_image
 
 
-class _Deferred:
-    """A prepared igemm launch whose split-K workspace is assigned once every launch of the engine is known."""
-    launch = None
-
-    def __call__(self):
-        self.launch()
-
-
 class _RaftEncoder(torch.autograd.Function):
     @staticmethod
     def forward(ctx, images, engine):
@@ -252,7 +232,7 @@ def encode(enc, images: torch.Tensor) -> torch.Tensor:
     """BasicEncoder.forward on the native engine (one engine per encoder, batch and frame size, cached on the module)."""
     from .flownetc_engine import _weights_stamp
     n, _, H, W = images.shape
-    key = (int(n), int(H), int(W), str(images.device), ig._PRODUCTS[-1])       # (the launches bake the products of their arithmetic in)
+    key = (int(n), int(H), int(W), str(images.device), ig.current_products())       # (the launches bake the products of their arithmetic in)
     cache = _engine_cache(enc, "_ufr_encoder_engines")
     stamp = _weights_stamp(enc) + tuple((b.data_ptr(), b._version) for b in enc.buffers())
     eng = cache.get(key)

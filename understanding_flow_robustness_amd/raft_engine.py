@@ -165,21 +165,18 @@ class RaftUpdateEngine:
             w_q[tag] = torch.cat([wq[:, 256:], wq[:, :128]], 1).contiguous()              # buffer: [motion | r*h]
             w_q_ctx[tag] = wq[:, 128:256].contiguous()
         self._pads = {"1": (0, 2), "2": (2, 0)}
-        plans = []
+        # ping-pong tiles with a deep split (>= 4 K tiles per slice) measured best on these 48 x 160 grids: 18.1 ms per
+        # iteration against 18.4 (>= 8), 19.8 (>= 16), 18.4 with 64 x 128 tiles and 18.6 with single-stage 128 x 128 tiles
+        # (capping the split because a second stream fills the chip anyway measured SLOWER: 16.02 ms -> 16.47 at <= 2 slices, 20.16
+        # without split-K, gpurun r5_call11: a lone ping-pong workgroup per CU is latency-bound, short slices are the cure)
+        queue, planned, ctx_of = ig.LaunchQueue(dev, min_ktiles=4, phases=1), {}, {}
+        self._side_keys = {"convf1", "convf2", "conv^T", "convc2^T", "convc1^T"}       # (the side stream's launches: two streams, below)
 
         def plan(key, wi, x, in_chunk0, ctx=None, **kw):
-            pk = [len(t) * wi.KC for _, _, t in wi.phases]
-            # ping-pong tiles with a deep split (>= 4 K tiles per slice) measured best on these 48 x 160 grids: 18.1 ms per
-            # iteration against 18.4 (>= 8), 19.8 (>= 16), 18.4 with 64 x 128 tiles and 18.6 with single-stage 128 x 128 tiles
             kw.setdefault("variant", 6 if wi.Npad % 128 == 0 else 2)
-            bm, target = (256, 256) if kw["variant"] == 6 else (128, 768)
-            S = ig.splitk_for(self.M, wi.Npad, max(pk), 1, phase_ktiles=pk, bm=bm, target=target, min_ktiles=4)
-            kw["variant"], S = ig.tuned(wi, self.M, kw, kw["variant"], S, rows=(h, w))
-            # (capping the split because a second stream fills the chip anyway measured SLOWER: 16.02 ms -> 16.47 at <= 2 slices, 20.16
-            # without split-K, gpurun r5_call11: a lone ping-pong workgroup per CU is latency-bound, short slices are the cure)
-            if ctx is not None and not (kw.get("no_reduce") and S > 1):
-                kw["add"] = ctx            # no slabs for the gate kernel to read: the context share rides in igemm's own epilogue
-            plans.append((key, wi, x, in_chunk0, S, kw))
+            planned[key] = queue.add(wi, x, in_chunk0, (h, w), (h, w), pool="side" if key[0] in self._side_keys else None, **kw)
+            if ctx is not None:
+                ctx_of[key] = ctx
 
         W = dict(convc1=cw(enc.convc1, 0), convc2=cw(enc.convc2, 1), convf1=cw(wf1, 0), convf2=cw(enc.convf2, 1), conv=cw(enc.conv, 1),
                  fh1=cw(ub.flow_head.conv1, 1), mask1=cw(ub.mask[0], 1), mask2=cw(ub.mask[2], 0))
@@ -236,16 +233,15 @@ class RaftUpdateEngine:
         #             of iteration i - 1.
         # The side stream's launches split K into their own workspace.  Inside a HIP-graph capture the fork / join events become
         # graph edges.  UFR_RAFT_STREAMS=0: everything on the caller's stream (the A/B switch).
-        self._side_keys = {"convf1", "convf2", "conv^T", "convc2^T", "convc1^T"}
-        side = lambda key: key[0] in self._side_keys
-        need = max([S * self.M * wi.Npad for key, wi, _, _, S, _ in plans if S > 1 and not side(key)] + [1])
-        need_side = max([S * self.M * wi.Npad for key, wi, _, _, S, _ in plans if S > 1 and side(key)] + [1])
-        self.ws, self.ws_side = torch.empty(need, **f32), torch.empty(need_side, **f32)
-        self.launch, self._wi = {}, {}
-        for key, wi, x, c0, S, kw in plans:
-            ws = (self.ws_side if side(key) else self.ws) if S > 1 else None
-            self.launch[key] = ig.make_launch(wi, x, c0, (h, w), (h, w), splitk=S, ws=ws, **kw)
-            self._wi[key] = wi
+        queue.plan()
+        for key, ctx in ctx_of.items():
+            p = planned[key]
+            if not (p.kw.get("no_reduce") and p.S > 1):
+                p.kw["add"] = ctx          # no slabs for the gate kernel to read: the context share rides in igemm's own epilogue
+        self.ws = queue.build()
+        self.ws_side = queue.ws["side"]
+        self.launch = {key: p.launch for key, p in planned.items()}
+        self._wi = {key: p.wi for key, p in planned.items()}
         self._two_streams = os.environ.get("UFR_RAFT_STREAMS", "1") != "0"
         self._side_stream = torch.cuda.Stream(device=dev) if self._two_streams else None
         fh2 = ub.flow_head.conv2
@@ -490,7 +486,7 @@ class _RaftRefine(torch.autograd.Function):
 def get_engine(net, B: int, H: int, W: int, device) -> RaftUpdateEngine:
     from .flownetc_engine import _weights_stamp
     a = net.args            # the launch schedule bakes these in: a changed `args.iters` on a live model must rebuild it
-    key = (int(B), int(H), int(W), str(torch.device(device)), int(a.iters), int(a.corr_radius), int(a.corr_levels), ig._PRODUCTS[-1])
+    key = (int(B), int(H), int(W), str(torch.device(device)), int(a.iters), int(a.corr_radius), int(a.corr_levels), ig.current_products())
     cache = _engine_cache(net, "_ufr_head_engines")
     stamp = _weights_stamp(net)
     eng = cache.get(key)

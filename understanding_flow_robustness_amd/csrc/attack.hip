@@ -7,7 +7,7 @@
 
 namespace {
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+using ufr::dev::clampf;
 
 // main.py:537-542 / :585-600.  (1-m)*img and m*patch are rounded separately, then added -- the
 // reference's torch.mul + torch.mul + add (no fma).

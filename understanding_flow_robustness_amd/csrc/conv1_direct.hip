@@ -28,9 +28,10 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+using ufr::dev::bf16x8;
+using ufr::dev::f32x4;
+using ufr::dev::split3;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int TY = 8, TX = 32;                         // output pixels of a tile
 constexpr int RY = 2 * TY + 5, RX = 2 * TX + 5;        // input region: 21 x 69
@@ -40,13 +41,6 @@ constexpr int BUF_B = 3 * PLANE_B;                     // 36,288
 constexpr int PX_PER_THREAD = (RY * RX + 511) / 512;   // 3
 __device__ constexpr int PROD_W[6] = {2, 0, 1, 1, 0, 0};   // (weight plane, pixel plane) of each product, smallest first
 __device__ constexpr int PROD_X[6] = {0, 2, 1, 0, 1, 0};
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
 
 struct Conv1Args {
   const float* fa; const float* fb; int Ba, N, H, W;

@@ -21,23 +21,14 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using ufr::dev::bf16x8;
+using ufr::dev::f32x4;
+using ufr::dev::glds16;
+using ufr::dev::split3;
 
 __device__ constexpr int PROD_A[6] = {2, 0, 1, 1, 0, 0};
 __device__ constexpr int PROD_B[6] = {0, 2, 1, 0, 1, 0};
 __device__ __attribute__((aligned(64))) unsigned corr_zero_page[16];
-
-__device__ __forceinline__ void glds16(const __bf16* src, __bf16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
 
 constexpr int P = 21, R = 10, KCH = 8;           // 21 displacements per axis, reach 10 same-parity columns, 8 chunks of 32 channels
 constexpr int OT = 24;                            // per-wave output tile: 16 columns x 21 displacements, row stride 24 floats

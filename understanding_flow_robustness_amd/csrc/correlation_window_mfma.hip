@@ -21,18 +21,12 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using ufr::dev::bf16x8;
+using ufr::dev::f32x4;
+using ufr::dev::split3;
 
 __device__ constexpr int WPA[6] = {2, 0, 1, 1, 0, 0};
 __device__ constexpr int WPB[6] = {0, 2, 1, 0, 1, 0};
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
 
 constexpr int WP = 21, WR = 10, WC = 256;
 constexpr int AST = 72;                           // A row stride in bf16: 64 source columns + 8 (bank spread), 16-byte rows

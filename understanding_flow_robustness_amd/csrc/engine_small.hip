@@ -17,14 +17,9 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
+using ufr::dev::bf16x8;
+using ufr::dev::f32x4;
+using ufr::dev::split3;
 
 // wpk [chunks][9][2][32] float32: wpk[ch][k][o][c] = weight[o][32*ch + c][k] (zero for padding channels).
 // Workgroup = an 8 x 32 pixel tile of one image (thread = pixel, all 32 channels of a chunk) x S chunk slices.  Per chunk
@@ -183,7 +178,6 @@ __global__ __launch_bounds__(1024) void flow_head_planes_fwd_small(const __bf16*
 // load per plane, no LDS staging); float32 = six bf16 products (csrc/igemm.hip); T goes through LDS once.  Workgroup =
 // TH x 32 pixels (+ halo) x S chunk slices; wave = (slice, tile lane): m-tiles tw, tw + 4, ... of 16 halo pixels.
 // wmf: bf16 [chunks][3 planes][2 n-tiles][16][32]: plane p of w[o][32 ch + c][k] at n = 2k + o, zero for n >= 18.
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 __device__ constexpr int PFM_A[6] = {2, 0, 1, 1, 0, 0};
 __device__ constexpr int PFM_B[6] = {0, 2, 1, 0, 1, 0};
 __device__ __attribute__((aligned(64))) unsigned pf_zero_page[16];

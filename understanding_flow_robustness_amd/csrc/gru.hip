@@ -14,7 +14,7 @@
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+using ufr::dev::sigmoidf_;
 
 __global__ void gru_gates_fwd(const float* __restrict__ zr_pre, const float* __restrict__ h,
                               float* __restrict__ z_out, float* __restrict__ rh_out, long n_per_b, long total,

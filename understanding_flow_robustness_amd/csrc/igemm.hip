@@ -35,8 +35,10 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using ufr::dev::bf16x8;
+using ufr::dev::f32x4;
+using ufr::dev::glds16;
+using ufr::dev::split3;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int BM = 128, BN = 128, BK = 32;
@@ -49,13 +51,6 @@ struct RowGeom {            // what the kernels need to turn a tile row into pix
   int row_x0_stride, row_x0_div;
   int Ho, Wo, out_sy, out_sx;
 };
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
 
 // One output element through the epilogue.  `pout` = output pixel index, `n` = output channel.
 struct Epilogue {
@@ -100,11 +95,20 @@ __device__ __forceinline__ void epilogue_store(const Epilogue& e, long pout, int
   }
 }
 
-__device__ __forceinline__ long out_pixel(const RowGeom& g, int pm, int oy0, int ox0) {
+// Tile row pm -> (b, yr, xr) of the row grid, and the first column of sample b's band: the ONE decomposition that the staging
+// side (cell_geometry) and the output side (out_pixel) share.
+struct GridCell { int b, yr, xr; };
+__device__ __forceinline__ GridCell grid_cell(const RowGeom& g, int pm) {
   const int hw = g.Hr * g.Wr;
-  const int b = pm / hw, r = pm - b * hw, yr = r / g.Wr, xr = r - yr * g.Wr;
-  const int xg = xr + (g.row_x0 ? g.row_x0[b * g.row_x0_stride] / g.row_x0_div : 0);
-  return ((long)b * g.Ho + (yr * g.out_sy + oy0)) * g.Wo + (xg * g.out_sx + ox0);
+  const int b = pm / hw, r = pm - b * hw, yr = r / g.Wr;
+  return {b, yr, r - yr * g.Wr};
+}
+__device__ __forceinline__ int band_x0(const RowGeom& g, int b) { return g.row_x0 ? g.row_x0[b * g.row_x0_stride] / g.row_x0_div : 0; }
+
+__device__ __forceinline__ long out_pixel(const RowGeom& g, int pm, int oy0, int ox0) {
+  const GridCell c = grid_cell(g, pm);
+  const int xg = c.xr + band_x0(g, c.b);
+  return ((long)c.b * g.Ho + (c.yr * g.out_sy + oy0)) * g.Wo + (xg * g.out_sx + ox0);
 }
 
 // Eight consecutive channels of one output pixel through the epilogue (n0 a multiple of 8): 16-byte accesses.
@@ -422,9 +426,164 @@ __device__ __attribute__((aligned(64))) unsigned ufr_zero_page[16];
 __device__ unsigned long long* ufr_clock_probe_buf = nullptr;
 __device__ int ufr_clock_probe_cap = 0;
 
-// one LDS-DMA: 16 bytes per lane from `src` (per lane) to `lds_wave_base + 16 * lane` (the base must be wave-uniform)
-__device__ __forceinline__ void glds16(const __bf16* src, __bf16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
+// ---- what the three tile kernels share: the walk from launch index to K range, a cell's input geometry, the activation and
+// ---- weight stagers, the fragment offset and the product loop.  A kernel form = these + its own schedule.
+
+// Launch index -> (column tile, row tile, z) -> (phase, slice) -> K tiles [kt0, kt1).  TAIL_: the launch may carry a re-cut last
+// round (tail_tile; the ping-pong kernel only).
+struct TileWalk {
+  int tx, ty, z, phase, ks, kt0, kt1;
+  bool tail_slice;                   // a K slice of a tile of the re-cut last round
+  __device__ __forceinline__ int tile_id() const { return (phase * gridDim.y + ty) * gridDim.x + tx; }   // igemm_write_out's ticket
+};
+template <bool TAIL_ = false>
+__device__ __forceinline__ TileWalk tile_walk(const Args& a) {
+  TileWalk t;
+  t.tail_slice = false;
+  if (TAIL_ && a.tl_S) t.tail_slice = tail_tile(a, t.tx, t.ty, t.z);
+  else xcd_tile(a.xcd, t.tx, t.ty, t.z);
+  t.phase = 0;                       // z -> (phase, slice): phases with fewer taps have fewer slices
+#pragma unroll
+  for (int p = 1; p < 4; ++p)
+    if (p < a.nphase && t.z >= a.zoff[p]) t.phase = p;
+  t.ks = t.z - a.zoff[t.phase];
+  const int per_k = t.tail_slice ? a.tl_per_k : a.per_k;
+  t.kt0 = t.ks * per_k;
+  t.kt1 = min(a.ph[t.phase].ntaps * a.KC, t.kt0 + per_k);
+  return t;
+}
+
+// One cell (flat index into the row grid [B, Hr, Wr]; outside it: a dead row that no tap can reach) -> the input pixel of tap
+// (0, 0), the input columns that count, the sample's first input pixel.  xr_override >= 0 replaces the cell's column (the tap-reuse
+// kernel's pixels past a grid row's end).
+struct Cell {
+  int yb, xb, xlo, xhi;
+  long ibase;
+};
+__device__ __forceinline__ Cell cell_geometry(const Args& a, long cell, int xr_override) {
+  const bool live = cell >= 0 && cell < a.g.M;
+  const GridCell c = grid_cell(a.g, live ? (int)cell : 0);
+  const int xg = (xr_override >= 0 ? xr_override : c.xr) + band_x0(a.g, c.b);
+  Cell o;
+  o.yb = live ? c.yr * a.in_sy : -(1 << 20);
+  o.xb = xg * a.in_sx;
+  o.ibase = (long)c.b * a.Hi * a.Wi;
+  o.xlo = a.in_x0 ? a.in_x0[c.b * a.in_x0_stride] / a.in_x0_div : 0;
+  o.xhi = a.in_x0 ? min(a.Wi, o.xlo + a.in_xw) : a.Wi;
+  o.xlo = max(o.xlo, 0);
+  return o;
+}
+// is tap (dyo, dxo) of the cell inside the frame / band; its pixel index inside the sample
+__device__ __forceinline__ bool tap_pixel(const Args& a, const Cell& c, int dyo, int dxo, int& pix) {
+  const int yi = c.yb + dyo, xi = c.xb + dxo;
+  pix = yi * a.Wi + xi;
+  return (unsigned)yi < (unsigned)a.Hi && xi >= c.xlo && xi < c.xhi;
+}
+
+// The activation rows of a tile, one tap and one channel chunk at a time: lane (row srow0 + 64 i, piece csw) of APT x 64 rows,
+// NPL planes, into LDS images of IMG_ROWS rows per plane.  BUF_: through a raw buffer resource (see igemm_pp_kernel).
+template <int APT, int NPL, int IMG_ROWS, bool BUF_>
+struct ActStager {
+  Cell cell[APT];
+  bool ok[APT];
+  long aoff[APT];                    // pointer form: elements from the chunk's start to the row's pixel
+  unsigned voff[APT], rowbase[APT];  // BUF_: byte offset of the row's piece, or out of range
+  __amdgpu_buffer_rsrc_t rsrc;
+  const __bf16 *gx, *xk;             // pointer form: chunk in_chunk0 / the current chunk, at this lane's piece
+  long xkoff, cstride;               // BUF_: elements from plane 0 to the current chunk
+  int tap, kc;
+
+  __device__ __forceinline__ void init(const Args& a, const Phase& ph, int bm, int srow0, int csw, int kt0) {
+    cstride = (long)a.g.B * a.Hi * a.Wi * 32;
+#pragma unroll
+    for (int i = 0; i < APT; ++i) {
+      cell[i] = cell_geometry(a, bm + srow0 + 64 * i, -1);
+      rowbase[i] = (unsigned)(cell[i].ibase * 64 + csw * 16);
+    }
+    gx = a.x + (long)a.in_chunk0 * cstride + csw * 8;
+    tap = a.korder ? kt0 % ph.ntaps : kt0 / a.KC;
+    kc = a.korder ? kt0 / ph.ntaps : kt0 - tap * a.KC;
+    xk = gx + (long)kc * cstride;
+    rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.x), 0, (int)min(6L * a.x_plane_stride, 0x7fffffffL), 0x00020000);
+    xkoff = (long)(a.in_chunk0 + kc) * cstride;
+  }
+  __device__ __forceinline__ void set_tap(const Args& a, const Phase& ph, int t) {
+    const int dyx = ph.dyx[t], dyo = (int)(short)(dyx & 0xffff), dxo = dyx >> 16;
+#pragma unroll
+    for (int i = 0; i < APT; ++i) {
+      int pix;
+      ok[i] = tap_pixel(a, cell[i], dyo, dxo, pix);
+      if (BUF_) voff[i] = ok[i] ? rowbase[i] + (unsigned)pix * 64u : 0x80000000u;
+      else aoff[i] = ok[i] ? (cell[i].ibase + (long)pix) * 32 : 0;
+    }
+  }
+  // the rows of the next K tile -> the image at `lds` (wave-uniform: lane l lands at the wave's 16 rows + 16 l bytes), then
+  // advance over (tap, chunk) in the launch's K order
+  __device__ __forceinline__ void stage(const Args& a, const Phase& ph, __bf16* lds, int wave) {
+#pragma unroll
+    for (int i = 0; i < APT; ++i)
+#pragma unroll
+      for (int p = 0; p < NPL; ++p) {
+        __bf16* dst = lds + p * (IMG_ROWS * BK) + (64 * i + wave * 16) * BK;
+        if constexpr (BUF_) {
+          typedef __attribute__((address_space(3))) void* lds_void;
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void)dst, 16, (int)voff[i], (unsigned)((xkoff + p * a.x_plane_stride) * 2), 0, 0);
+        } else {
+          glds16(ok[i] ? xk + aoff[i] + p * a.x_plane_stride : reinterpret_cast<const __bf16*>(ufr_zero_page), dst);
+        }
+      }
+    if (a.korder) {                  // the taps of one channel chunk back to back: their pixels overlap, so they hit in L2
+      if (++tap == ph.ntaps) {
+        tap = 0;
+        xk += cstride;
+        xkoff += cstride;
+      }
+      set_tap(a, ph, tap);
+    } else {
+      xk += cstride;
+      xkoff += cstride;
+      if (++kc == a.KC) {
+        kc = 0;
+        xk = gx;
+        xkoff = (long)a.in_chunk0 * cstride;
+        if (++tap < ph.ntaps) set_tap(a, ph, tap);
+      }
+    }
+  }
+};
+
+// the weight rows of one K tile (BN_ columns, NPL planes) -> the image at `lds`; the caller steps `wp` to the next K tile
+template <int BN_, int NPL>
+__device__ __forceinline__ void stage_weights(const __bf16* wp, long w_plane_stride, __bf16* lds, int wave) {
+#pragma unroll
+  for (int i = 0; i < BN_ / 64; ++i)
+#pragma unroll
+    for (int p = 0; p < NPL; ++p)
+      glds16(wp + p * w_plane_stride + (long)(64 * i) * BK, lds + p * (BN_ * BK) + (64 * i + wave * 16) * BK);
+}
+
+template <int MT>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[MT][4]) {
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// element offset of a lane's 16-byte fragment piece inside the 16 swizzled rows of an MFMA operand
+__device__ __forceinline__ int frag_offset(int lane) {
+  const int frow = lane & 15;
+  return frow * BK + ((((lane >> 4)) ^ ((frow >> 1) & 3)) << 3);
+}
+// one K step of the register-held forms: per column tile n, the products smallest first, per row tile m
+template <int NPL, int MT, int FIRST>
+__device__ __forceinline__ void mfma_products(const bf16x8 (&fa)[NPL][MT], const bf16x8 (&fb)[4][NPL], f32x4 (&acc)[MT][4]) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n)
+#pragma unroll
+    for (int t = FIRST; t < 6; ++t)
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[PROD_A[t]][m], fb[n][PROD_B[t]], acc[m][n], 0, 0, 0);
 }
 
 // BM_ x BN_ tiles: 128 x 128 (waves 2 x 2 of 64 x 64), 128 x 64 (waves 4 x 1 of 32 x 64: layers with <= 64 outputs), and
@@ -444,7 +603,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE_ ? 2 :
   static_assert(NP_ == 6 || NP_ == 3 || NP_ == 1, "six, three or one product");
   constexpr int NPL = NP_ == 6 ? 3 : (NP_ == 3 ? 2 : 1), FIRST = 6 - NP_;
   constexpr int MT = (BN_ == 128 && BM_ == 128) ? 4 : 2;
-  constexpr int BPT = BN_ / 64, APT = BM_ / 64;
+  constexpr int APT = BM_ / 64;
   constexpr int STAGE = NPL * (BM_ + BN_) * BK;       // elements of one (A, B) stage; PIPE_ appends a second A image
   constexpr int EPI = 4 * 32 * 68 * 2;                // elements the epilogue's transpose needs (one- / two-plane stages are smaller)
   __shared__ __attribute__((aligned(16))) __bf16 lds_static[PIPE_ ? 8 : (STAGE > EPI ? STAGE : EPI)];
@@ -454,102 +613,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE_ ? 2 :
   __bf16 (*ldsB)[BN_ * BK] = reinterpret_cast<__bf16 (*)[BN_ * BK]>(lds_all + NPL * BM_ * BK);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wrow = BN_ == 128 ? (wave >> 1) * (BM_ / 2) : wave * 32, wcol = BN_ == 128 ? (wave & 1) * 64 : 0;
-  int tx, ty, z;
-  xcd_tile(a.xcd, tx, ty, z);
-  const int bm = ty * BM_, bn = tx * BN_;
-  int phase = 0;                                     // z -> (phase, slice): phases with fewer taps have fewer slices
-#pragma unroll
-  for (int p = 1; p < 4; ++p)
-    if (p < a.nphase && z >= a.zoff[p]) phase = p;
-  const int ks = z - a.zoff[phase];
-  const Phase& ph = a.ph[phase];
-  const int KC = a.KC, KT = ph.ntaps * KC;
-  const int kt0 = ks * a.per_k, kt1 = min(KT, kt0 + a.per_k);
-  const long Min = (long)a.g.B * a.Hi * a.Wi;
-  const long cstride = Min * 32;
+  const TileWalk wk = tile_walk(a);
+  const int bm = wk.ty * BM_, bn = wk.tx * BN_, kt0 = wk.kt0, kt1 = wk.kt1;
+  const Phase& ph = a.ph[wk.phase];
 
   const int srow0 = tid >> 2, sch = tid & 3;
   const int csw = sch ^ ((srow0 >> 1) & 3);             // the piece this lane fetches (64 more rows keep (row >> 1) & 3)
-  int yb[APT], xb[APT], xlo[APT], xhi[APT];
-  long ibase[APT];
-#pragma unroll
-  for (int i = 0; i < APT; ++i) {
-    const int pm = bm + srow0 + 64 * i;
-    const int hw = a.g.Hr * a.g.Wr;
-    const int b = pm / hw, r = pm - b * hw, yr = r / a.g.Wr, xr = r - yr * a.g.Wr;
-    const bool live = pm < a.g.M;
-    const int bb = live ? b : 0;
-    const int xg = xr + (a.g.row_x0 ? a.g.row_x0[bb * a.g.row_x0_stride] / a.g.row_x0_div : 0);
-    yb[i] = live ? yr * a.in_sy : -(1 << 20);
-    xb[i] = xg * a.in_sx;
-    ibase[i] = (long)bb * a.Hi * a.Wi;
-    xlo[i] = a.in_x0 ? a.in_x0[bb * a.in_x0_stride] / a.in_x0_div : 0;
-    xhi[i] = a.in_x0 ? min(a.Wi, xlo[i] + a.in_xw) : a.Wi;
-    xlo[i] = max(xlo[i], 0);
-  }
-  const __bf16* gx = a.x + (long)a.in_chunk0 * cstride + csw * 8;
-  const __bf16* zero = reinterpret_cast<const __bf16*>(ufr_zero_page);
-  int tap = a.korder ? kt0 % ph.ntaps : kt0 / KC, kc = a.korder ? kt0 / ph.ntaps : kt0 - tap * KC;
+  ActStager<APT, NPL, BM_, BUF_> act;
+  act.init(a, ph, bm, srow0, csw, kt0);
   const __bf16* wp = a.w + ph.w_off + ((long)kt0 * a.Npad + bn + srow0) * BK + csw * 8;
   const long wstep = (long)a.Npad * BK;
-  const __bf16* xk = gx + (long)kc * cstride;
-  bool ok[APT];
-  long aoff[APT];
-  unsigned voff[APT], rowbase[APT];
-#pragma unroll
-  for (int i = 0; i < APT; ++i) rowbase[i] = (unsigned)(ibase[i] * 64 + csw * 16);
-  __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.x), 0, (int)min(6L * a.x_plane_stride, 0x7fffffffL),
-                                                                   0x00020000);
-  long xkoff = (long)(a.in_chunk0 + kc) * cstride;
-  auto set_tap = [&](int t) {
-    const int dyx = ph.dyx[t], dyo = (int)(short)(dyx & 0xffff), dxo = dyx >> 16;
-#pragma unroll
-    for (int i = 0; i < APT; ++i) {
-      const int yi = yb[i] + dyo, xi = xb[i] + dxo;
-      ok[i] = (unsigned)yi < (unsigned)a.Hi && xi >= xlo[i] && xi < xhi[i];
-      if (BUF_) voff[i] = ok[i] ? rowbase[i] + (unsigned)(yi * a.Wi + xi) * 64u : 0x80000000u;
-      else aoff[i] = ok[i] ? (ibase[i] + (long)yi * a.Wi + xi) * 32 : 0;
-    }
-  };
-  // wave-uniform LDS destinations: the wave's 16 rows of each image (lane l lands at base + 16 l bytes)
-  auto stage_A = [&](int img) {      // the activation rows of the next K tile -> LDS image at element `img`, then advance (tap, chunk)
-#pragma unroll
-    for (int i = 0; i < APT; ++i)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p) {
-        if constexpr (BUF_) {                 // (single-stage form only: the static array)
-          typedef __attribute__((address_space(3))) void* lds_void;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void)(lds_static + img + p * (BM_ * BK) + (64 * i + wave * 16) * BK), 16, (int)voff[i],
-                                                   (unsigned)((xkoff + p * a.x_plane_stride) * 2), 0, 0);
-        } else {
-          const __bf16* src = ok[i] ? xk + aoff[i] + p * a.x_plane_stride : zero;
-          glds16(src, lds_all + img + p * (BM_ * BK) + (64 * i + wave * 16) * BK);
-        }
-      }
-    if (a.korder) {                  // the taps of one channel chunk back to back: their pixels overlap, so they hit in L2
-      if (++tap == ph.ntaps) {
-        tap = 0;
-        xk += cstride;
-        xkoff += cstride;
-      }
-      set_tap(tap);
-    } else {
-      xk += cstride;
-      xkoff += cstride;
-      if (++kc == KC) {
-        kc = 0;
-        xk = gx;
-        xkoff = (long)a.in_chunk0 * cstride;
-        if (++tap < ph.ntaps) set_tap(tap);
-      }
-    }
-  };
+  // (BUF_ is a single-stage form: the static array, whose address the compiler knows)
+  auto stage_A = [&](int img) { act.stage(a, ph, (BUF_ ? lds_static : lds_all) + img, wave); };
   auto stage_B = [&]() {             // the weight rows of the next K tile
-#pragma unroll
-    for (int i = 0; i < BPT; ++i)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p)
-        glds16(wp + p * a.w_plane_stride + (long)(64 * i) * BK, &ldsB[p][(64 * i + wave * 16) * BK]);
+    stage_weights<BN_, NPL>(wp, a.w_plane_stride, &ldsB[0][0], wave);
     wp += wstep;
   };
   auto stage_tile = [&]() {
@@ -558,14 +635,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE_ ? 2 :
   };
 
   f32x4 acc[MT][4];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int frow = lane & 15;
-  const int foff = frow * BK + ((((lane >> 4)) ^ ((frow >> 1) & 3)) << 3);
+  zero_acc(acc);
+  const int foff = frag_offset(lane);
 
-  if (kt0 < kt1) set_tap(tap);
+  if (kt0 < kt1) act.set_tap(a, ph, act.tap);
   if constexpr (PIPE_) {
     // two activation images (the second behind the stage), one weight image.  Step kt: [all DMA landed, barrier] -> DMA of
     // A(kt + 1) into the other image (its last readers finished before the previous step's second barrier) -> 24 fragment
@@ -594,13 +667,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE_ ? 2 :
       __builtin_amdgcn_s_barrier();  // every wave holds its fragments: the weight image is free
       if (kt + 1 < kt1) stage_B();
       __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-      for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int t = FIRST; t < 6; ++t)
-#pragma unroll
-          for (int m = 0; m < MT; ++m)
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[PROD_A[t]][m], fb[n][PROD_B[t]], acc[m][n], 0, 0, 0);
+      mfma_products<NPL, MT, FIRST>(fa, fb, acc);
     }
   } else
   for (int kt = kt0; kt < kt1; ++kt) {
@@ -626,8 +693,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PIPE_ ? 2 :
     }
   }
   static_assert(PIPE_ ? 4 * 32 * 68 * 4 <= STAGE * 2 : true, "epilogue staging does not fit");
-  igemm_write_out<NPL, MT, BM_, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_all), reinterpret_cast<int*>(lds_all), z, phase,
-                                     (phase * gridDim.y + ty) * gridDim.x + tx, bm, bm, bn, bn, wrow, wcol, lane, wave);
+  igemm_write_out<NPL, MT, BM_, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_all), reinterpret_cast<int*>(lds_all), wk.z, wk.phase,
+                                     wk.tile_id(), bm, bm, bn, bn, wrow, wcol, lane, wave);
 }
 constexpr int PIPE_LDS_BYTES = (3 * (128 + 128) * BK + 3 * 128 * BK) * 2;     // one stage + the second activation image
 
@@ -656,7 +723,7 @@ template <int BN_, bool BUF_ = false, int NP_ = 6>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void igemm_pp_kernel(const Args a) {
   static_assert(NP_ == 6 || NP_ == 3 || NP_ == 1, "six, three or one product");
   constexpr int NPL = NP_ == 6 ? 3 : (NP_ == 3 ? 2 : 1), FIRST = 6 - NP_;      // (the images keep their three-plane size: one workgroup per CU)
-  constexpr int MT = BN_ == 128 ? 4 : 2, BPT = BN_ / 64;
+  constexpr int MT = BN_ == 128 ? 4 : 2;
   constexpr int PP_IMG_B = 3 * BN_ * BK;
   extern __shared__ __attribute__((aligned(16))) __bf16 lds_pp[];
   unsigned long long* const probe = ufr_clock_probe_buf;
@@ -665,118 +732,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);             // wave-uniform: LDS destinations on the scalar unit
   const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);      // wave-uniform: scalar control flow
   const int wrow = BN_ == 128 ? (wave >> 1) * 64 : wave * 32, wcol = BN_ == 128 ? (wave & 1) * 64 : 0;
-  int tx, ty, z;
-  bool tail_slice = false;                                                 // a K slice of a tile of the re-cut last round (tail_tile)
-  if (a.tl_S) tail_slice = tail_tile(a, tx, ty, z);
-  else xcd_tile(a.xcd, tx, ty, z);
-  const int bm = ty * 256 + grp * 128, bn = tx * BN_;
-  int phase = 0;
-#pragma unroll
-  for (int p = 1; p < 4; ++p)
-    if (p < a.nphase && z >= a.zoff[p]) phase = p;
-  const int ks = z - a.zoff[phase];
-  const Phase& ph = a.ph[phase];
-  const int KC = a.KC, KT = ph.ntaps * KC;
-  const int per_k = tail_slice ? a.tl_per_k : a.per_k;
-  const int kt0 = ks * per_k, kt1 = min(KT, kt0 + per_k);
-  const int nk = max(kt1 - kt0, 0);
-  const long Min = (long)a.g.B * a.Hi * a.Wi;
-  const long cstride = Min * 32;
+  const TileWalk wk = tile_walk<true>(a);
+  const int bm = wk.ty * 256 + grp * 128, bn = wk.tx * BN_;
+  const Phase& ph = a.ph[wk.phase];
+  const int nk = max(wk.kt1 - wk.kt0, 0);
 
   const int srow0 = tid >> 2, sch = tid & 3;
   const int csw = sch ^ ((srow0 >> 1) & 3);
-  int yb[2], xb[2], xlo[2], xhi[2];
-  long ibase[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int pm = bm + srow0 + 64 * i;
-    const int hw = a.g.Hr * a.g.Wr;
-    const int b = pm / hw, r = pm - b * hw, yr = r / a.g.Wr, xr = r - yr * a.g.Wr;
-    const bool live = pm < a.g.M;
-    const int bb = live ? b : 0;
-    const int xg = xr + (a.g.row_x0 ? a.g.row_x0[bb * a.g.row_x0_stride] / a.g.row_x0_div : 0);
-    yb[i] = live ? yr * a.in_sy : -(1 << 20);
-    xb[i] = xg * a.in_sx;
-    ibase[i] = (long)bb * a.Hi * a.Wi;
-    xlo[i] = a.in_x0 ? a.in_x0[bb * a.in_x0_stride] / a.in_x0_div : 0;
-    xhi[i] = a.in_x0 ? min(a.Wi, xlo[i] + a.in_xw) : a.Wi;
-    xlo[i] = max(xlo[i], 0);
-  }
-  const __bf16* gx = a.x + (long)a.in_chunk0 * cstride + csw * 8;
-  const __bf16* zero = reinterpret_cast<const __bf16*>(ufr_zero_page);
-  int tap = a.korder ? kt0 % ph.ntaps : kt0 / KC, kc = a.korder ? kt0 / ph.ntaps : kt0 - tap * KC;
-  const __bf16* wp = a.w + ph.w_off + ((long)kt0 * a.Npad + bn + srow0) * BK + csw * 8;
+  ActStager<2, NPL, 128, BUF_> act;
+  act.init(a, ph, bm, srow0, csw, wk.kt0);
+  const __bf16* wp = a.w + ph.w_off + ((long)wk.kt0 * a.Npad + bn + srow0) * BK + csw * 8;
   const long wstep = (long)a.Npad * BK;
-  const __bf16* xk = gx + (long)kc * cstride;
-  bool ok[2];
-  long aoff[2];
-  unsigned voff[2];                                                        // BUF_: byte offset of the row's piece, or out of range
-  const unsigned rowbase[2] = {(unsigned)(ibase[0] * 64 + csw * 16), (unsigned)(ibase[1] * 64 + csw * 16)};
-  __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.x), 0, (int)min(6L * a.x_plane_stride, 0x7fffffffL),
-                                                                   0x00020000);
-  long xkoff = (long)(a.in_chunk0 + kc) * cstride;                         // BUF_: elements from plane 0 to the current chunk
-  auto set_tap = [&](int t) {
-    const int dyx = ph.dyx[t], dyo = (int)(short)(dyx & 0xffff), dxo = dyx >> 16;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int yi = yb[i] + dyo, xi = xb[i] + dxo;
-      ok[i] = (unsigned)yi < (unsigned)a.Hi && xi >= xlo[i] && xi < xhi[i];
-      if (BUF_) voff[i] = ok[i] ? rowbase[i] + (unsigned)(yi * a.Wi + xi) * 64u : 0x80000000u;
-      else aoff[i] = ok[i] ? (ibase[i] + (long)yi * a.Wi + xi) * 32 : 0;
-    }
-  };
   const int imgA0 = grp * 2 * PP_IMG, imgB0 = 4 * PP_IMG;                 // element offsets: A[grp][0..1], B[0..1]
-  auto stage_A = [&](int img) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p) {
-        if (BUF_) {
-          typedef __attribute__((address_space(3))) void* lds_void;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void)(lds_pp + img + p * (128 * BK) + (64 * i + wave * 16) * BK), 16, (int)voff[i],
-                                                   (unsigned)((xkoff + p * a.x_plane_stride) * 2), 0, 0);
-        } else {
-          const __bf16* src = ok[i] ? xk + aoff[i] + p * a.x_plane_stride : zero;
-          glds16(src, lds_pp + img + p * (128 * BK) + (64 * i + wave * 16) * BK);
-        }
-      }
-    if (a.korder) {
-      if (++tap == ph.ntaps) {
-        tap = 0;
-        xk += cstride;
-        xkoff += cstride;
-      }
-      set_tap(tap);
-    } else {
-      xk += cstride;
-      xkoff += cstride;
-      if (++kc == KC) {
-        kc = 0;
-        xk = gx;
-        xkoff = (long)a.in_chunk0 * cstride;
-        if (++tap < ph.ntaps) set_tap(tap);
-      }
-    }
-  };
+  auto stage_A = [&](int img) { act.stage(a, ph, lds_pp + img, wave); };
   auto stage_B = [&](int img) {
-#pragma unroll
-    for (int i = 0; i < BPT; ++i)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p)
-        glds16(wp + p * a.w_plane_stride + (long)(64 * i) * BK, lds_pp + img + p * (BN_ * BK) + (64 * i + wave * 16) * BK);
+    stage_weights<BN_, NPL>(wp, a.w_plane_stride, lds_pp + img, wave);
     wp += wstep;
   };
 
   f32x4 acc[MT][4];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int frow = lane & 15;
-  const int foff = frow * BK + ((((lane >> 4)) ^ ((frow >> 1) & 3)) << 3);
+  zero_acc(acc);
+  const int foff = frag_offset(lane);
 
   if (nk > 0) {
-    set_tap(tap);
+    act.set_tap(a, ph, act.tap);
     stage_A(imgA0);
     if (grp == 0) stage_B(imgB0);
   }
@@ -809,19 +788,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();
     // ---- MFMA half-step (the other group reads)
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int t = FIRST; t < 6; ++t)
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[PROD_A[t]][m], fb[n][PROD_B[t]], acc[m][n], 0, 0, 0);
+    mfma_products<NPL, MT, FIRST>(fa, fb, acc);
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();                             // group 1's extra barrier at the start
   const unsigned long long probe_c3 = probe ? __builtin_amdgcn_s_memtime() : 0;
   static_assert(4 * 32 * 68 * 4 <= 2 * PP_IMG * 2, "epilogue staging does not fit a group's activation images");
-  igemm_write_out<NPL, MT, 256, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_pp + imgA0), reinterpret_cast<int*>(lds_pp), z, phase,
-                                     (phase * gridDim.y + ty) * gridDim.x + tx, ty * 256, bm, bn, bn, wrow, wcol, lane, wave, tail_slice);
+  igemm_write_out<NPL, MT, 256, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_pp + imgA0), reinterpret_cast<int*>(lds_pp), wk.z, wk.phase,
+                                     wk.tile_id(), wk.ty * 256, bm, bn, bn, wrow, wcol, lane, wave, wk.tail_slice);
   if (probe && threadIdx.x == 0) {
     const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     if (wg < ufr_clock_probe_cap) {                                       // 8 words per workgroup: cycles at entry / exit, 100 MHz
@@ -850,55 +823,33 @@ constexpr int pp3_lds_bytes(int bn) { return (4 * PP3_IMG + 2 * 3 * bn * BK) * 2
 // the activation rows are 80 % of a K step's L2 -> LDS bytes and the plain forms are bound by that delivery): 4 x 1 of 32 x 64.
 template <int BN_>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void igemm_pp3_kernel(const Args a) {
-  constexpr int NPL = 3, MT = BN_ == 128 ? 4 : 2, BPT = BN_ / 64, PP_IMG_B = 3 * BN_ * BK;
+  constexpr int NPL = 3, MT = BN_ == 128 ? 4 : 2, PP_IMG_B = 3 * BN_ * BK;
   extern __shared__ __attribute__((aligned(16))) __bf16 lds_pp[];
   const int tid = threadIdx.x & 255, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);
   const int wrow = BN_ == 128 ? (wave >> 1) * 64 : wave * 32, wcol = BN_ == 128 ? (wave & 1) * 64 : 0;
-  int tx, ty, z;
-  xcd_tile(a.xcd, tx, ty, z);
-  const int bm = ty * 256 + grp * 128, bn = tx * BN_;
-  int phase = 0;
-#pragma unroll
-  for (int p = 1; p < 4; ++p)
-    if (p < a.nphase && z >= a.zoff[p]) phase = p;
-  const int ks = z - a.zoff[phase];
-  const Phase& ph = a.ph[phase];
-  const int ntaps = ph.ntaps, KT = ntaps * a.KC;
-  const int kt0 = ks * a.per_k, kt1 = min(KT, kt0 + a.per_k);
-  const int nk = max(kt1 - kt0, 0);
-  const long Min = (long)a.g.B * a.Hi * a.Wi;
-  const long cstride = Min * 32;
-  const int Wr = a.g.Wr, hw = a.g.Hr * Wr;
+  const TileWalk wk = tile_walk(a);
+  const int bm = wk.ty * 256 + grp * 128, bn = wk.tx * BN_;
+  const Phase& ph = a.ph[wk.phase];
+  const int ntaps = ph.ntaps, kt0 = wk.kt0;
+  const int nk = max(wk.kt1 - kt0, 0);
+  const long cstride = (long)a.g.B * a.Hi * a.Wi * 32;
+  const int Wr = a.g.Wr;
 
   // ---- staging geometry: image rows srow0, srow0 + 64 (cells of the tile) and, on wave 0, extra row 128 + (lane >> 2)
   const int srow0 = tid >> 2, sch = tid & 3;
   const int csw = sch ^ ((srow0 >> 1) & 3);
   const int xrow = lane >> 2, cswx = sch ^ ((xrow >> 1) & 3);             // (128 + xrow) >> 1 & 3 == xrow >> 1 & 3
-  int yb[3], xb[3], xlo[3], xhi[3];
-  long ibase[3];
-  auto cell_geometry = [&](int i, long cell, int xr_override) {            // cell = flat index into [B, Hr, Wr]
-    const bool live = cell >= 0 && cell < a.g.M;
-    const int c = live ? (int)cell : 0;
-    const int b = c / hw, r = c - b * hw, yr = r / Wr;
-    const int xr = xr_override >= 0 ? xr_override : r - yr * Wr;
-    const int xg = xr + (a.g.row_x0 ? a.g.row_x0[b * a.g.row_x0_stride] / a.g.row_x0_div : 0);
-    yb[i] = live ? yr * a.in_sy : -(1 << 20);
-    xb[i] = xg * a.in_sx;
-    ibase[i] = (long)b * a.Hi * a.Wi;
-    xlo[i] = a.in_x0 ? a.in_x0[b * a.in_x0_stride] / a.in_x0_div : 0;
-    xhi[i] = a.in_x0 ? min(a.Wi, xlo[i] + a.in_xw) : a.Wi;
-    xlo[i] = max(xlo[i], 0);
-  };
-  cell_geometry(0, (long)bm + srow0, -1);
-  cell_geometry(1, (long)bm + srow0 + 64, -1);
+  Cell cg[3];
+  cg[0] = cell_geometry(a, (long)bm + srow0, -1);
+  cg[1] = cell_geometry(a, (long)bm + srow0 + 64, -1);
   const int grow0 = bm / Wr;                                              // first grid row (flat over B * Hr) the tile touches
   if (xrow < 2) {
-    cell_geometry(2, (long)bm + 128 + xrow, -1);
+    cg[2] = cell_geometry(a, (long)bm + 128 + xrow, -1);
   } else {                                                                // pixel (xrow & 1) + 1 past the end of grid row grow0 + e
     const int e = (xrow - 2) >> 1, w = (xrow - 2) & 1;
     const long rowcell = (long)(grow0 + e) * Wr;                          // that grid row's first cell
-    cell_geometry(2, rowcell < a.g.M ? rowcell : -1, Wr + w);
+    cg[2] = cell_geometry(a, rowcell < a.g.M ? rowcell : -1, Wr + w);
   }
   const __bf16* gx = a.x + (long)a.in_chunk0 * cstride + csw * 8;
   const __bf16* gxx = a.x + (long)a.in_chunk0 * cstride + cswx * 8;
@@ -913,28 +864,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const long coff = (long)kc * cstride;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int yi = yb[i] + dyo, xi = xb[i] + dxo;
-      const bool ok = (unsigned)yi < (unsigned)a.Hi && xi >= xlo[i] && xi < xhi[i];
-      const long off = ok ? (ibase[i] + (long)yi * a.Wi + xi) * 32 + coff : 0;
+      int pix;
+      const bool ok = tap_pixel(a, cg[i], dyo, dxo, pix);
+      const long off = ok ? (cg[i].ibase + (long)pix) * 32 + coff : 0;
 #pragma unroll
       for (int p = 0; p < NPL; ++p)
         glds16(ok ? gx + off + p * a.x_plane_stride : zero, lds_pp + img + p * (PP3_ROWS * BK) + (64 * i + wave * 16) * BK);
     }
     if (wave == 0) {                                                      // the 16 extra rows: lane -> (row 128 + lane / 4, piece)
-      const int yi = yb[2] + dyo, xi = xb[2] + dxo;
-      const bool ok = (unsigned)yi < (unsigned)a.Hi && xi >= xlo[2] && xi < xhi[2];
-      const long off = ok ? (ibase[2] + (long)yi * a.Wi + xi) * 32 + coff : 0;
+      int pix;
+      const bool ok = tap_pixel(a, cg[2], dyo, dxo, pix);
+      const long off = ok ? (cg[2].ibase + (long)pix) * 32 + coff : 0;
 #pragma unroll
       for (int p = 0; p < NPL; ++p)
         glds16(ok ? gxx + off + p * a.x_plane_stride : zero, lds_pp + img + p * (PP3_ROWS * BK) + 128 * BK);
     }
   };
   auto stage_B = [&](int img) {
-#pragma unroll
-    for (int i = 0; i < BPT; ++i)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p)
-        glds16(wp + p * a.w_plane_stride + (long)(64 * i) * BK, lds_pp + img + p * (BN_ * BK) + (64 * i + wave * 16) * BK);
+    stage_weights<BN_, NPL>(wp, a.w_plane_stride, lds_pp + img, wave);
     wp += wstep;
   };
 
@@ -952,13 +899,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       foffs[m][sft] = r * BK + (((lane >> 4) ^ ((r >> 1) & 3)) << 3);
     }
   }
-  const int fboff = frow * BK + (((lane >> 4) ^ ((frow >> 1) & 3)) << 3);
+  const int fboff = frag_offset(lane);
 
   f32x4 acc[MT][4];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   // ---- K steps kt = chunk * ntaps + tap (chunk-major: the host requires k_order = 1)
   int kc = kt0 / ntaps, tap = kt0 - kc * ntaps;
@@ -1002,13 +946,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();
     // ---- MFMA half-step
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[PROD_A[t]][m], fb[n][PROD_B[t]], acc[m][n], 0, 0, 0);
+    mfma_products<NPL, MT, 0>(fa, fb, acc);
     // advance (kc, tap); a new run flips the image
     first_of_run = pos == len - 1;
     if (first_of_run) ebuf ^= 1;
@@ -1016,8 +954,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();
   static_assert(4 * 32 * 68 * 4 <= 2 * PP3_IMG * 2, "epilogue staging does not fit a group's activation images");
-  igemm_write_out<NPL, MT, 256, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_pp + imgA0), reinterpret_cast<int*>(lds_pp), z, phase,
-                                     (phase * gridDim.y + ty) * gridDim.x + tx, ty * 256, bm, bn, bn, wrow, wcol, lane, wave);
+  igemm_write_out<NPL, MT, 256, BN_>(a, ph, acc, reinterpret_cast<float*>(lds_pp + imgA0), reinterpret_cast<int*>(lds_pp), wk.z, wk.phase,
+                                     wk.tile_id(), wk.ty * 256, bm, bn, bn, wrow, wcol, lane, wave);
 }
 
 // ---- direct 3 x 3 form (variant 8, round 5): stride-1 3 x 3 convolutions with at most 64 output columns -- the full- and
@@ -1156,6 +1094,54 @@ std::atomic<int> g_variant_fallbacks{0};     // launches that asked for variant 
 extern "C" int ufr_igemm_variant_fallbacks(void) { return g_variant_fallbacks.load(); }
 
 namespace {
+// The single-stage / ping-pong tile of one shape, activation rows through the buffer resource where the planes allow it (the pointer
+// forms exist for six products only).
+template <int BM_, int BN_, int NP_>
+void launch_glds(const Args& a, dim3 grid, bool use_buf, hipStream_t st) {
+  if (use_buf) igemm_glds_kernel<BM_, BN_, false, true, NP_><<<grid, 256, 0, st>>>(a);
+  else if constexpr (NP_ == 6) igemm_glds_kernel<BM_, BN_><<<grid, 256, 0, st>>>(a);
+}
+template <int NP_>
+void launch_pp(const Args& a, dim3 grid, bool use_buf, hipStream_t st) {
+  if (use_buf) igemm_pp_kernel<128, true, NP_><<<grid, 512, pp_lds_bytes(128), st>>>(a);
+  else if constexpr (NP_ == 6) igemm_pp_kernel<128><<<grid, 512, pp_lds_bytes(128), st>>>(a);
+}
+
+// The tile forms of one launch, NP_ products: the four tile shapes -- ping-pong 256 x 128, 64 x 128, 128 x 128, 128 x 64 -- once; six
+// products add the tap-reuse and the pipelined form, which reduced products (RAFT's opt-in bf16 arithmetic) run as their plain twins.
+template <int NP_>
+int launch_tiles(const Args& a, const ufr_igemm_desc* d, const ufr_igemm_tail_plan_t* tp, int variant, int nz, bool use_buf, hipStream_t st) {
+  const long M = a.g.M;
+  // 64-column tiles where a 128-column tile would be mostly padding.  (64-column tiles ON REQUEST for launches whose columns are a
+  // multiple of 128 -- twice the workgroups per split-K slice, so half the slabs on RAFT's 48 x 160 grids -- won the cold per-launch
+  // sweep on the four GRU launches by 3 - 15 % and LOST inside the step: 16.18 ms against 16.02 / 16.02 with the table without them,
+  // same call, gpurun r5_call30.  Removed.)
+  const int bn = d->Npad % BN == 0 ? BN : 64;
+  const dim3 grid(d->Npad / bn, (unsigned)((M + BM - 1) / BM), nz);
+  if constexpr (NP_ != 6) UFR_REQUIRE(use_buf, "igemm: the reduced-product forms need activation planes below 2 GB");
+  if (NP_ == 6 && variant == 7 && d->k_order && (d->in_sx == 1 || d->in_sx == 2) && d->Wr >= 22) {
+    // ping-pong + horizontal runs of taps staged once (launches it does not cover fall through to the plain forms)
+    const dim3 gpp(d->Npad / bn, (unsigned)((M + 255) / 256), nz);
+    if (bn == BN) igemm_pp3_kernel<128><<<gpp, 512, pp3_lds_bytes(128), st>>>(a);
+    else igemm_pp3_kernel<64><<<gpp, 512, pp3_lds_bytes(64), st>>>(a);
+  } else if (variant == 4 && bn == BN) {                  // 64 x 128 tiles: four workgroups per CU
+    launch_glds<64, 128, NP_>(a, dim3(d->Npad / BN, (unsigned)((M + 63) / 64), nz), use_buf, st);
+  } else if ((variant == 6 || variant == 7 || (NP_ != 6 && variant == 5)) && bn == BN) {   // ping-pong: 256-row tiles, two wave groups half a step apart
+    if constexpr (NP_ != 6) {                             // (the six-product forms' limits are raised once per device, igemm_run)
+      const hipError_t e = ufr::ensure_dynamic_lds(reinterpret_cast<const void*>(igemm_pp_kernel<128, true, NP_>), pp_lds_bytes(128));
+      if (e != hipSuccess) return ufr::fail(UFR_ELAUNCH, "igemm: %s", hipGetErrorString(e));
+    }
+    launch_pp<NP_>(a, tp ? dim3(tp->workgroups) : dim3(d->Npad / BN, (unsigned)((M + 255) / 256), nz), use_buf, st);
+  } else if (NP_ == 6 && variant == 5 && bn == BN) {      // register-held fragments, DMA of the next tile under the MFMAs
+    igemm_glds_kernel<128, 128, true><<<grid, 256, PIPE_LDS_BYTES, st>>>(a);
+  } else if (bn == BN) {
+    launch_glds<128, 128, NP_>(a, grid, use_buf, st);
+  } else {
+    launch_glds<128, 64, NP_>(a, grid, use_buf, st);
+  }
+  return UFR_OK;
+}
+
 // ufr_igemm; with `tp` (a plan that is ON, ufr_igemm_balanced) the ping-pong launch whose last round is re-cut into K slices with
 // slabs in `tws`, and the reduce launch over the tail's rows.
 int igemm_run(const ufr_igemm_desc* d, const ufr_igemm_tail_plan_t* tp, float* tws, ufr_stream_t stream) {
@@ -1249,12 +1235,6 @@ int igemm_run(const ufr_igemm_desc* d, const ufr_igemm_tail_plan_t* tp, float* t
     nz += a.sk[z];
   }
   hipStream_t st = ufr::as_stream(stream);
-  // 64-column tiles where a 128-column tile would be mostly padding.  (64-column tiles ON REQUEST for launches whose columns are a
-  // multiple of 128 -- twice the workgroups per split-K slice, so half the slabs on RAFT's 48 x 160 grids -- won the cold per-launch
-  // sweep on the four GRU launches by 3 - 15 % and LOST inside the step: 16.18 ms against 16.02 / 16.02 with the table without them,
-  // same call, gpurun r5_call30.  Removed.)
-  const int bn = d->Npad % BN == 0 ? BN : 64;
-  const dim3 grid(d->Npad / bn, (unsigned)((M + BM - 1) / BM), nz);
   // kernel forms: 0 / 2 = single-stage LDS-DMA tiles (128 x 128, or 128 x 64 where Npad is not a multiple of 128),
   // 4 = 64 x 128 tiles (four workgroups per CU), 5 = pipelined 128 x 128, 6 = ping-pong 256 x 128 (128-column launches only;
   // the 64-column ones run the single-stage 128 x 64 tile, which measured faster there), 7 = ping-pong with horizontal runs of
@@ -1299,50 +1279,9 @@ int igemm_run(const ufr_igemm_desc* d, const ufr_igemm_tail_plan_t* tp, float* t
     if (e != hipSuccess) return ufr::fail(UFR_ELAUNCH, "igemm (direct 3 x 3): %s", hipGetErrorString(e));
     return ufr::launched("igemm_d33_kernel");
   }
-  if (d->products != 6) {
-    // reduced products (RAFT's opt-in bf16 arithmetic): the single-stage tiles, the 64 x 128 tiles and the ping-pong tiles, activation rows
-    // through the buffer resource; the pipelined / tap-reuse / direct forms run as their plain twins
-    UFR_REQUIRE(use_buf, "igemm: the reduced-product forms need activation planes below 2 GB");
-#define UFR_NP_LAUNCH(NP_)                                                                                                    \
-    if ((variant == 6 || variant == 7 || variant == 5) && bn == BN) {                                                          \
-      const dim3 gpp(d->Npad / BN, (unsigned)((M + 255) / 256), nz);                                                           \
-      hipError_t e = ufr::ensure_dynamic_lds(reinterpret_cast<const void*>(igemm_pp_kernel<128, true, NP_>), pp_lds_bytes(128)); \
-      if (e != hipSuccess) return ufr::fail(UFR_ELAUNCH, "igemm: %s", hipGetErrorString(e));                                   \
-      igemm_pp_kernel<128, true, NP_><<<gpp, 512, pp_lds_bytes(128), st>>>(a);                                                 \
-    } else if (variant == 4 && bn == BN) {                                                                                     \
-      const dim3 g64(d->Npad / BN, (unsigned)((M + 63) / 64), nz);                                                             \
-      igemm_glds_kernel<64, 128, false, true, NP_><<<g64, 256, 0, st>>>(a);                                                    \
-    } else if (bn == BN) {                                                                                                     \
-      igemm_glds_kernel<128, 128, false, true, NP_><<<grid, 256, 0, st>>>(a);                                                  \
-    } else {                                                                                                                   \
-      igemm_glds_kernel<128, 64, false, true, NP_><<<grid, 256, 0, st>>>(a);                                                   \
-    }
-    if (d->products == 3) { UFR_NP_LAUNCH(3) } else { UFR_NP_LAUNCH(1) }
-#undef UFR_NP_LAUNCH
-  } else
-  if (variant == 7 && d->k_order && (d->in_sx == 1 || d->in_sx == 2) && d->Wr >= 22) {
-    // ping-pong + horizontal runs of taps staged once (launches it does not cover fall through to the plain forms)
-    const dim3 gpp(d->Npad / bn, (unsigned)((M + 255) / 256), nz);
-    if (bn == BN) igemm_pp3_kernel<128><<<gpp, 512, pp3_lds_bytes(128), st>>>(a);
-    else igemm_pp3_kernel<64><<<gpp, 512, pp3_lds_bytes(64), st>>>(a);
-  } else if (variant == 4 && bn == BN) {                  // 64 x 128 tiles: four workgroups per CU
-    const dim3 g64(d->Npad / BN, (unsigned)((M + 63) / 64), nz);
-    if (use_buf) igemm_glds_kernel<64, 128, false, true><<<g64, 256, 0, st>>>(a);
-    else igemm_glds_kernel<64, 128><<<g64, 256, 0, st>>>(a);
-  } else if ((variant == 6 || variant == 7) && bn == BN) {           // ping-pong: 256-row tiles, two wave groups half a step apart
-    const dim3 gpp = tp ? dim3(tp->workgroups) : dim3(d->Npad / BN, (unsigned)((M + 255) / 256), nz);
-    if (use_buf) igemm_pp_kernel<128, true><<<gpp, 512, pp_lds_bytes(128), st>>>(a);
-    else igemm_pp_kernel<128><<<gpp, 512, pp_lds_bytes(128), st>>>(a);
-  } else if (variant == 5 && bn == BN) {           // register-held fragments, DMA of the next tile under the MFMAs
-    igemm_glds_kernel<128, 128, true><<<grid, 256, PIPE_LDS_BYTES, st>>>(a);
-  } else if (bn == BN) {
-    if (use_buf) igemm_glds_kernel<128, 128, false, true><<<grid, 256, 0, st>>>(a);
-    else igemm_glds_kernel<128, 128><<<grid, 256, 0, st>>>(a);
-  } else {
-    if (use_buf) igemm_glds_kernel<128, 64, false, true><<<grid, 256, 0, st>>>(a);
-    else igemm_glds_kernel<128, 64><<<grid, 256, 0, st>>>(a);
-  }
-  int rc = ufr::launched("igemm_kernel");
+  int rc = d->products == 6 ? launch_tiles<6>(a, d, tp, variant, nz, use_buf, st)
+                            : (d->products == 3 ? launch_tiles<3>(a, d, tp, variant, nz, use_buf, st) : launch_tiles<1>(a, d, tp, variant, nz, use_buf, st));
+  if (rc == UFR_OK) rc = ufr::launched("igemm_kernel");
   if (rc != UFR_OK || (!tp && (d->splitk == 1 || d->no_reduce || a.tickets))) return rc;   // no_reduce: the caller's next kernel adds the slabs itself;
                                                                                   // tickets: the last workgroup of every tile already has
   const long total = tp ? (long)tp->tail_rows * (d->Npad / 8) : (long)d->nphase * M * (d->Npad / 8);

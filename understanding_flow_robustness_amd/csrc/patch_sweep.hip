@@ -20,7 +20,8 @@ constexpr int kSlots = 128;            // workgroups (= partials) per position a
 constexpr int kSums = 3;               // valid * epe, valid * cos, valid
 constexpr int kWinInts = 8;            // win[k] = {y0, x0, need_h, need_w, ymin, ymax, xmin, xmax} (window.hip)
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+using ufr::dev::clampf;
+using ufr::dev::cone_axis;
 
 // attack.hip's paste_placed_kernel, do_clamp = 1: (1-m)*img and m*patch are rounded separately, then added (no fma)
 __device__ __forceinline__ float paste_clamped(float img, float m, float pv, float lo, float hi) {
@@ -75,37 +76,7 @@ __global__ __launch_bounds__(kBlock) void sweep_paste_canvas_kernel(const float*
   }
 }
 
-// ---- window form, first launch: the window table ------------------------------------------------------------------------------
-__device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-__device__ __forceinline__ int ceil_div_i(int a, int b) { return -floor_div(-a, b); }
-
-// window.hip's cone_axis, statement for statement (ufr_cone_window and ufr_attack_place run it; the tests compare the tables bit for
-// bit): [lo, hi] (input pixels, inclusive) -> window origin / needed extent in pixels.
-__device__ void cone_axis(int lo, int hi, int size, const ufr_cone_chain& ch, int win, int* origin, int* need) {
-  int total = 1;
-  for (int l = 0; l < ch.n_layers; ++l) total *= ch.stride[l];
-  const int cells = size / total;
-  if (hi < lo) { *origin = 0; *need = 0; return; }
-  int need_lo = INT_MAX, need_hi = -1, n = size, jump = 1, t = 0;
-  for (int l = 0; l < ch.n_layers; ++l) {
-    const int k = ch.kernel[l], s = ch.stride[l], p = ch.pad[l];
-    const int n_out = (n + 2 * p - k) / s + 1;
-    lo = max(ceil_div_i(lo + p - (k - 1), s), 0);
-    hi = min(floor_div(hi + p, s), n_out - 1);
-    n = n_out; jump *= s;
-    while (t < ch.n_taps && ch.tap_layer[t] == l) {
-      const int per = total / jump;
-      need_lo = min(need_lo, floor_div(lo - ch.tap_margin[t], per));
-      need_hi = max(need_hi, floor_div(hi + ch.tap_margin[t], per));
-      ++t;
-    }
-  }
-  need_lo = max(need_lo, 0); need_hi = min(need_hi, cells - 1);
-  const int cnt = need_hi - need_lo + 1, wcells = win / total;
-  int o = need_lo - max(wcells - cnt, 0) / 2;
-  o = min(max(o, 0), max(cells - wcells, 0));
-  *origin = o * total; *need = cnt * total;
-}
+// ---- window form, first launch: the window table (window.hip's cone_axis: ufr_common.h) -----------------------------------------
 
 // One workgroup: the box of mask_p != 0 (all channels), then per position the table ufr_cone_window computes from the canvas mask,
 // whose box is origin + that box (the host has checked that every placement lies inside the frame).
@@ -198,16 +169,7 @@ __global__ __launch_bounds__(kBlock) void sweep_paste_window_kernel(const float*
 }
 
 // ---- metrics ------------------------------------------------------------------------------------------------------------------
-// the sum over the workgroup in a fixed order, returned to every thread (train_loss.hip)
-__device__ inline double block_sum(double v, double* lds) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();                                            // the previous use of lds is over
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < kBlock / 64; ++i) t += lds[i];
-  return t;
-}
+using ufr::dev::block_sum;          // the sum over the workgroup in a fixed order, returned to every thread
 
 // torch's upsample_bilinear2d, align_corners = False, size given (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index):
 //   src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out;  i0 = (int)src;  i1 = i0 + (i0 < in - 1);  l1 = src - i0
@@ -275,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __re
     sum[2] += g[2];
   }
   for (int q = 0; q < kSums; ++q) {
-    const double t = block_sum(sum[q], lds);
+    const double t = block_sum<kBlock>(sum[q], lds);
     if (threadIdx.x == 0) part[((long)k * kSlots + blockIdx.x) * kSums + q] = t;
   }
 }
@@ -287,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void sweep_metrics_finalize_kernel(const do
   const int k = blockIdx.x;
   double t[kSums];
   for (int q = 0; q < kSums; ++q)
-    t[q] = block_sum((int)threadIdx.x < slots ? part[((long)k * kSlots + threadIdx.x) * kSums + q] : 0.0, lds);
+    t[q] = block_sum<kBlock>((int)threadIdx.x < slots ? part[((long)k * kSlots + threadIdx.x) * kSums + q] : 0.0, lds);
   if (threadIdx.x == 0) {
     const double den = t[2] + 1e-8;                                               // losses.py:22
     out[2 * k] = (float)(t[0] / den);

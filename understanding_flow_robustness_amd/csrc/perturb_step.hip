@@ -19,8 +19,8 @@ constexpr int kBlock = 256;
 constexpr int kMaxPartials = 2048;         // workgroups of a launch: 8 per CU, the rest is a grid stride
 constexpr long kPerGroup = 1024;           // elements per workgroup before the grid stops growing
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
-__device__ __forceinline__ float signf(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }  // torch.sign (NaN -> 0)
+using ufr::dev::clampf;
+using ufr::dev::signf;
 
 __host__ __device__ inline int groups_for(long n) {
   const long g = (n + kPerGroup - 1) / kPerGroup;

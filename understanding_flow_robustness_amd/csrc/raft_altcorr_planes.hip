@@ -27,8 +27,10 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using ufr::dev::bf16x8;
+using ufr::dev::f32x4;
+using ufr::dev::glds16;
+using ufr::dev::split3;
 
 __device__ constexpr int PROD_A[6] = {2, 0, 1, 1, 0, 0};   // (a plane, b plane) of each product, smallest first (igemm.hip)
 __device__ constexpr int PROD_B[6] = {0, 2, 1, 0, 1, 0};
@@ -44,17 +46,6 @@ struct PlaneLevels {                              // by value in the kernel argu
   int H2[4], W2[4];
   float cscale[4];
 };
-
-__device__ __forceinline__ void glds16(const __bf16* src, __bf16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
 
 // NHWC float32 [npix][C] -> planes bf16 [3][C / 32][npix][32]; thread = (pixel, 8 channels): two 16-byte reads, three 16-byte writes
 __global__ __launch_bounds__(256) void altcorr_planes_prepare_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long plane_stride,

@@ -12,47 +12,17 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
-
-__device__ __forceinline__ void load_planes8(const __bf16* p, long plane_stride, float v[8]) {
-  const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-  const bf16x8 b = *reinterpret_cast<const bf16x8*>(p + plane_stride);
-  const bf16x8 c = *reinterpret_cast<const bf16x8*>(p + 2 * plane_stride);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = ((float)a[j] + (float)b[j]) + (float)c[j];
-}
-
-__device__ __forceinline__ void store_planes8(__bf16* p, long plane_stride, const float v[8]) {
-  bf16x8 q0, q1, q2;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 x, y, z;
-    split3(v[j], x, y, z);
-    q0[j] = x; q1[j] = y; q2[j] = z;
-  }
-  *reinterpret_cast<bf16x8*>(p) = q0;
-  *reinterpret_cast<bf16x8*>(p + plane_stride) = q1;
-  *reinterpret_cast<bf16x8*>(p + 2 * plane_stride) = q2;
-}
-
-__device__ __forceinline__ void load_f8(const float* p, float v[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
+using ufr::dev::bf16x8;
+using ufr::dev::load_f8;
+using ufr::dev::load_planes8;
+using ufr::dev::sigmoidf_;
+using ufr::dev::split3;
+using ufr::dev::store_planes8;
 
 __device__ __forceinline__ void store_f8(float* p, const float v[8]) {
   *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // planes[chunk0 + k / 32][(b, y, x)][k % 32] = flow[b, k & 1, y + (k >> 1) / 7 - 3, x + (k >> 1) % 7 - 3], k < 98 (0 outside)
 __global__ void flow_patches_kernel(const float* __restrict__ flow, __bf16* __restrict__ planes, long plane_stride, int chunk0,

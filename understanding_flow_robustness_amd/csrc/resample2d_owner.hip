@@ -23,7 +23,7 @@
 
 namespace {
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+using ufr::dev::clampi;
 
 constexpr int OT_H = 16, OT_W = 64;            // output tiles of kernel A = the table's granularity
 constexpr int RT_H = 16, RT_W = 64;            // owner tiles of kernel B

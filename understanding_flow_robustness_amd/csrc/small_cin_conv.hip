@@ -11,15 +11,9 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+using ufr::dev::bf16x8;
+using ufr::dev::split3;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-__device__ __forceinline__ void split3(float v, __bf16& a, __bf16& b, __bf16& c) {
-  a = (__bf16)v;
-  const float r1 = v - (float)a;
-  b = (__bf16)r1;
-  c = (__bf16)(r1 - (float)b);
-}
 
 template <int NG_>                               // NG_ groups of 8 output channels
 __global__ __launch_bounds__(256) void conv3x3s2_c3_planes_kernel(const float* __restrict__ x, const float* __restrict__ wgt,

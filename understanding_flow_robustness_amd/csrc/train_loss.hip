@@ -30,16 +30,7 @@ __device__ inline int find_scale(const int* wg0, int n, int wg) {
   return s;
 }
 
-// the sum over the workgroup in a fixed order, returned to every thread
-__device__ inline double block_sum(double v, double* lds) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  __syncthreads();                                            // the previous use of lds is over
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < kBlock / 64; ++i) t += lds[i];
-  return t;
-}
+using ufr::dev::block_sum;          // the sum over the workgroup in a fixed order, returned to every thread
 
 __global__ __launch_bounds__(kBlock) void gt_area_kernel(Scales sc, const float* __restrict__ gt, int B, int H, int W, double div_flow,
                                                          double* __restrict__ gtm, double* __restrict__ cnt) {
@@ -75,8 +66,8 @@ __global__ __launch_bounds__(kBlock) void gt_area_kernel(Scales sc, const float*
       n_pix += (ok0 && ok1) ? 1.0 : 0.0;
     }
   }
-  n_elem = block_sum(n_elem, lds);
-  n_pix = block_sum(n_pix, lds);
+  n_elem = block_sum<kBlock>(n_elem, lds);
+  n_pix = block_sum<kBlock>(n_pix, lds);
   if (threadIdx.x == 0) {
     cnt[((long)s * kSlots + wg) * 2 + 0] = n_elem;
     cnt[((long)s * kSlots + wg) * 2 + 1] = n_pix;
@@ -88,7 +79,7 @@ __device__ inline double scale_count(const Scales& sc, int s, int kind, const do
   const int n1 = sc.wg1[s + 1] - sc.wg1[s];
   double c = 0.0;
   for (int i = threadIdx.x; i < n1; i += kBlock) c += cnt[((long)s * kSlots + i) * 2 + kind];
-  return block_sum(c, lds);
+  return block_sum<kBlock>(c, lds);
 }
 
 __global__ __launch_bounds__(kBlock) void loss_grad_kernel(Scales sc, ufr_train_loss_desc d, const double* __restrict__ gtm,
@@ -147,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void loss_grad_kernel(Scales sc, ufr_train_
     grad[i1] = (float)g1;
   }
   for (int k = 0; k < kSums; ++k) {
-    const double t = block_sum(sum[k], lds);
+    const double t = block_sum<kBlock>(sum[k], lds);
     if (threadIdx.x == 0) part[((long)s * kSlots + wg) * kSums + k] = t;
   }
 }
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void loss_finalize_kernel(Scales sc, int ki
     const double count = scale_count(sc, s, kind, cnt, lds);
     const int n2 = sc.wg2[s + 1] - sc.wg2[s];                  // <= kSlots = kBlock: one partial per thread
     for (int k = 0; k < (s == 0 ? kSums : 1); ++k) {
-      const double t = block_sum((int)threadIdx.x < n2 ? part[((long)s * kSlots + threadIdx.x) * kSums + k] : 0.0, lds);
+      const double t = block_sum<kBlock>((int)threadIdx.x < n2 ? part[((long)s * kSlots + threadIdx.x) * kSums + k] : 0.0, lds);
       if (k == 0) {
         if (kind == 0 || count > 0.0) loss += sc.weight[s] * (t / count);        // kind 0: an empty mean is 0/0 = NaN, as in torch
       } else {

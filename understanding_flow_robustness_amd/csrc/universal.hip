@@ -8,8 +8,8 @@
 
 namespace {
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
-__device__ __forceinline__ float signf(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }  // torch.sign
+using ufr::dev::clampf;
+using ufr::dev::signf;
 
 // perturb_model.py:128-145.  kind 0 cossim, 1 l2 (+10e-8 inside the sqrt), 2 l1 (sum of |du|,|dv|
 // averaged over B*2*H*W elements when unmasked -- `loss.mean()` of a [B,2,H,W] tensor).

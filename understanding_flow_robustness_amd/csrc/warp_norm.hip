@@ -8,7 +8,7 @@
 
 namespace {
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+using ufr::dev::clampi;
 
 // resample2d_kernel.cu:15-72.  Quirks kept: clamp with the OUTPUT's dims (:45-48); the four
 // products are formed in double and rounded to float one by one (:52-55); nearest = floor(x+.5).

@@ -54,37 +54,8 @@ __global__ void bbox_kernel(const float* __restrict__ mask, long bstride, int C,
   }
 }
 
-__device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-__device__ __forceinline__ int ceil_div_i(int a, int b) { return -floor_div(-a, b); }
-
-// One axis: [lo, hi] (input pixels, inclusive) -> window origin / needed extent in pixels.
-// Cone of an interval through conv(k, s, p): outputs o with [s*o - p, s*o - p + k - 1] meeting it.
-__device__ void cone_axis(int lo, int hi, int size, const ufr_cone_chain& ch, int win, int* origin,
-                          int* need) {
-  int total = 1;
-  for (int l = 0; l < ch.n_layers; ++l) total *= ch.stride[l];
-  const int cells = size / total;          // window grid = cells of the deepest level
-  if (hi < lo) { *origin = 0; *need = 0; return; }
-  int need_lo = INT_MAX, need_hi = -1, n = size, jump = 1, t = 0;
-  for (int l = 0; l < ch.n_layers; ++l) {
-    const int k = ch.kernel[l], s = ch.stride[l], p = ch.pad[l];
-    const int n_out = (n + 2 * p - k) / s + 1;
-    lo = max(ceil_div_i(lo + p - (k - 1), s), 0);
-    hi = min(floor_div(hi + p, s), n_out - 1);
-    n = n_out; jump *= s;
-    while (t < ch.n_taps && ch.tap_layer[t] == l) {
-      const int per = total / jump;        // cells of this level per window-grid cell
-      need_lo = min(need_lo, floor_div(lo - ch.tap_margin[t], per));
-      need_hi = max(need_hi, floor_div(hi + ch.tap_margin[t], per));
-      ++t;
-    }
-  }
-  need_lo = max(need_lo, 0); need_hi = min(need_hi, cells - 1);
-  const int cnt = need_hi - need_lo + 1, wcells = win / total;
-  int o = need_lo - max(wcells - cnt, 0) / 2;
-  o = min(max(o, 0), max(cells - wcells, 0));
-  *origin = o * total; *need = cnt * total;
-}
+using ufr::dev::cone_axis;          // one axis of the window cone (ufr_common.h)
+using ufr::dev::floor_div;
 
 __global__ void cone_finalize_kernel(int* __restrict__ win, int N, int H, int W, ufr_cone_chain ch, int win_h,
                                      int win_w, float* __restrict__ overflow) {

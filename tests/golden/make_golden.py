@@ -96,6 +96,9 @@ def gen_ops():
 
 
 # ------------------------------------------------------------------------------------------ RAFT corr
+RAFT_CORR_16X24_SEED = 22
+
+
 def gen_raft_corr():
     """CorrBlock (models/raft/corr.py:26-106): all-pairs pyramid + lookup.  It is also the pin for
     alt_cuda_corr, whose values equal CorrBlock's."""
@@ -110,6 +113,19 @@ def gen_raft_corr():
     out = blk(coords)
     save("raft_corrblock_lookup", fmap1=f1, fmap2=f2, coords=coords, output=out,
          level0=blk.corr_pyramid[0], level3=blk.corr_pyramid[3])
+    # At 12 x 16 level 3 is 1 x 2 and CorrBlock's grid_sample normalisation divides by H - 1 = 0: channels 243..323 of the output
+    # above are not finite (the tests record that as a fact and pin levels 0-2 only).  At 16 x 24 level 3 is 2 x 3 and every
+    # level pins.  (level0 is left out: 2 * 384 * 384 floats would not fit a committed file; level 3 is stored.)
+    g = torch.Generator().manual_seed(RAFT_CORR_16X24_SEED)
+    B, C, H, W = 2, 32, 16, 24
+    f1 = torch.randn(B, C, H, W, generator=g)
+    f2 = torch.randn(B, C, H, W, generator=g)
+    coords = coords_grid(B, H, W) + 3.0 * torch.randn(B, 2, H, W, generator=g)
+    blk = corr_mod.CorrBlock(f1, f2, num_levels=4, radius=4)
+    out = blk(coords)
+    assert tuple(blk.corr_pyramid[3].shape[-2:]) == (2, 3) and tuple(out.shape) == (B, 4 * 81, H, W)
+    assert bool(torch.isfinite(out).all()), "raft_corrblock_lookup_16x24: the reference's output is not finite"
+    save("raft_corrblock_lookup_16x24", fmap1=f1, fmap2=f2, coords=coords, output=out, level3=blk.corr_pyramid[3])
 
 
 # ------------------------------------------------------------------------------------------ reference library

@@ -53,7 +53,7 @@ def encoder_heads(net, x1, x2, model_path=False):
 
 def check_encoder(z, outs, grads):
     """FlowNetC's gates (tests/test_flownetc_flex_gpu.py:100-104)."""
-    from conftest import assert_close
+    from closeness import assert_close
     for name, o in zip(("fmap1", "fmap2", "net0", "inp"), outs):
         assert_close(o, t(z[name]), rtol=1e-4, atol_scale=1e-5, what=name)
     for name, g in zip(("g1", "g2"), grads):

@@ -8,7 +8,8 @@ from argparse import Namespace
 import pytest
 import torch
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

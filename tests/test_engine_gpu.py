@@ -64,7 +64,8 @@ def test_engine_head_forward_and_gradients_match_the_torch_head(net, monkeypatch
 def test_engine_whole_network_vs_reference_golden(net, monkeypatch):
     """FlowNetC forward + image gradients through the engine against the reference's golden vectors."""
     import numpy as np
-    from conftest import assert_close, load_golden, t
+    from closeness import assert_close
+    from conftest import load_golden, t
     monkeypatch.setenv("UFR_ENGINE", "1")
     z = load_golden("flownetc_fwd_64x128")
     x1, x2 = t(z["x1"], DEV).requires_grad_(True), t(z["x2"], DEV).requires_grad_(True)

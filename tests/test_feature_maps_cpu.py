@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, assert_close, load_golden, t
+from closeness import assert_close
+from conftest import GOLDEN, load_golden, t
 
 KEY_SETS = {"conv3ab": ("conv3a", "conv3b"), "corr": ("corr",), "conv_redir": ("conv_redir",), "conv3_1": ("conv3_1",),
             "conv3a_alone": ("conv3a",), "conv4": ("conv4",)}

@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import assert_close, t
+from closeness import assert_close
+from conftest import t
 from test_feature_maps_cpu import KEY_SETS, frames, golden_flex, golden_flownetc
 
 pytestmark = pytest.mark.gpu

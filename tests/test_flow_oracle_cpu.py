@@ -4,7 +4,8 @@ EPE / cosine metrics); the host-side pieces of the product that need no GPU are 
 import pytest
 import torch
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 
 ATTACK_CASES = [("cos_lr1000", False, 1000.0), ("l2_lr1000", True, 1000.0), ("cos_lr5", False, 5.0),
                 ("l2_lr1", True, 1.0), ("cos_lr1e6", False, 1.0e6)]

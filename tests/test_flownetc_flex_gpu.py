@@ -8,7 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

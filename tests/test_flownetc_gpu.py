@@ -5,7 +5,8 @@ from argparse import Namespace
 import pytest
 import torch
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 from test_flow_oracle_cpu import ATTACK_CASES
 
 pytestmark = pytest.mark.gpu

@@ -3,7 +3,7 @@
 import pytest
 import torch
 
-from conftest import assert_close
+from closeness import assert_close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

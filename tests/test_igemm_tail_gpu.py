@@ -221,7 +221,7 @@ def test_captured_graph_follows_the_band_origins():
         launch()                                                      # (first call: the kernel's LDS limit is raised outside the capture)
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with L.graph_capture(graph):          # (no cyclic collection inside a capture: _lib.graph_capture)
         launch()
     ws = torch.empty(plan.slices * _B3 * _H3 * _RW * 256, device=DEV)
     for k in (0, 1, 0):

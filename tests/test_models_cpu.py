@@ -4,7 +4,8 @@ from argparse import Namespace
 
 import torch
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 
 
 def _sd(cls_factory, seed, golden):

@@ -5,7 +5,8 @@ from argparse import Namespace
 import pytest
 import torch
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -135,6 +136,7 @@ def test_universal_attack_vs_reference(use_graph):
         diff = (d.cpu() - ref_d).abs()
         assert float((diff > 1e-6).float().mean()) < 2e-3, f"{tag}: {float((diff > 1e-6).float().mean()):.2e} differ"
         assert float(diff.max()) <= 3 * 2e-3 * 2 + 1e-6
+        assert bool(torch.isfinite(a0).all()), f"{tag}: adv0 is not finite"          # (NaN is never "beyond": the share below cannot see it)
         assert float(((a0.cpu() - t(z[f"{tag}_adv0"])).abs() > 1e-6).float().mean()) < 2e-3
 
 
@@ -155,6 +157,7 @@ def test_universal_shared_batch_step_vs_oracle(oracle):
     _, _, d = fo.universal_attack(lambda a, b: fo.flownetc_forward(sd, a, b), img0, img1, delta0, target, n_step=2,
                                   shared=True)
     diff = (step.delta.cpu() - d).abs()
+    assert bool(torch.isfinite(diff).all()), "the perturbation is not finite"     # (NaN is never "beyond": the share below cannot see it)
     assert float((diff > 1e-6).float().mean()) < 2e-3
 
 

@@ -5,8 +5,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import assert_close, load_golden, t
-from test_oracle_cpu import CORR_CASES, expand_params
+from closeness import assert_close
+from conftest import load_golden, t
+from test_oracle_cpu import (CORR_CASES, CORRBLOCK_CASES, CORRBLOCK_TOL, assert_matches_corrblock_golden, corrblock_level3,
+                             expand_params)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -175,9 +177,12 @@ def _alt_inputs(B, H, W, C, g, spread=3.0, N=1):
     return f1, f2, coords.contiguous()
 
 
-def test_altcorr_matches_corrblock_golden(ops):
-    """alt_cuda_corr values == CorrBlock values (reference's own identity, models/raft/corr.py)."""
-    z = load_golden("raft_corrblock_lookup")
+@pytest.mark.parametrize("case", CORRBLOCK_CASES)
+def test_altcorr_matches_corrblock_golden(ops, oracle, case):
+    """alt_cuda_corr values == CorrBlock values (reference's own identity, models/raft/corr.py): all 324 channels at 16 x 24;
+    at 12 x 16 levels 0-2, and level 3 -- where CorrBlock's grid_sample normalisation yields NaN and alt_cuda_corr computes finite
+    values (test_oracle_cpu.py::assert_matches_corrblock_golden) -- against the oracle's alt_cuda_corr."""
+    z = load_golden(case)
     f1, f2, coords = t(z["fmap1"], DEV), t(z["fmap2"], DEV), t(z["coords"], DEV)
     B, C, H, W = f1.shape
     outs, f2l = [], f2
@@ -188,7 +193,10 @@ def test_altcorr_matches_corrblock_golden(ops):
         if i < 3:
             f2l = torch.nn.functional.avg_pool2d(f2l, 2, stride=2)
     alt = torch.stack(outs, dim=1).reshape(B, -1, H, W) / np.sqrt(C)
-    assert_close(alt, t(z["output"]), rtol=1e-4, atol_scale=2e-6, what="alt_corr vs CorrBlock golden")
+    assert_matches_corrblock_golden(alt, z, what=f"{case}: alt_corr vs CorrBlock golden")
+    c3 = (coords.permute(0, 2, 3, 1) / 8).reshape(B, 1, H, W, 2).contiguous().cpu()
+    (ref3,) = oracle.altcorr_forward(f1.permute(0, 2, 3, 1).contiguous().cpu(), f2l.permute(0, 2, 3, 1).contiguous().cpu(), c3, 4)
+    assert_close(corrblock_level3(alt), ref3.squeeze(1) / np.sqrt(C), what=f"{case}: level 3 vs the oracle's alt_cuda_corr", **CORRBLOCK_TOL)
 
 
 @pytest.mark.parametrize("B,H,W,C,r", [(1, 48, 160, 256, 4), (2, 13, 17, 64, 3), (1, 6, 20, 96, 4)])
@@ -373,9 +381,10 @@ def test_altcorr_dense_adjoint_vs_oracle(oracle, B, H, W, C, r, spread):
 
 
 # ---------------------------------------------------------------------------- CorrBlock lookup
-def test_lookup_matches_corrblock_golden_and_oracle(ops, oracle):
+@pytest.mark.parametrize("case", CORRBLOCK_CASES)
+def test_lookup_matches_corrblock_golden_and_oracle(ops, oracle, case):
     from understanding_flow_robustness_amd.flownets.raft_corr import corr_lookup
-    z = load_golden("raft_corrblock_lookup")
+    z = load_golden(case)
     f1, f2, coords = t(z["fmap1"], DEV), t(z["fmap2"], DEV), t(z["coords"], DEV)
     B, C, H, W = f1.shape
     corr = torch.matmul(f1.view(B, C, H * W).transpose(1, 2), f2.view(B, C, H * W)) / np.sqrt(C)
@@ -384,9 +393,10 @@ def test_lookup_matches_corrblock_golden_and_oracle(ops, oracle):
         pyr.append(torch.nn.functional.avg_pool2d(pyr[-1], 2, stride=2))
     pyr = [p.contiguous().requires_grad_(True) for p in pyr]
     out = corr_lookup(pyr, coords, 4)
-    assert_close(out, t(z["output"]), rtol=1e-4, atol_scale=2e-6, what="lookup vs CorrBlock golden")
+    assert_matches_corrblock_golden(out, z, what=f"{case}: lookup vs CorrBlock golden")
     ref = oracle.corr_lookup([p.detach().cpu() for p in pyr], coords.cpu(), 4)
-    assert_close(out, ref, rtol=1e-5, atol_scale=1e-6, what="lookup vs oracle")
+    assert_close(out, ref, rtol=1e-5, atol_scale=1e-6, what="lookup vs oracle")      # all four levels, level 3 included
+    assert_close(corrblock_level3(out), corrblock_level3(ref), what=f"{case}: level 3 vs the oracle's lookup", **CORRBLOCK_TOL)
     # adjoint against torch autograd through grid_sample (the reference's own formulation)
     go = torch.randn(out.shape, generator=torch.Generator().manual_seed(1)).to(DEV)
     out.backward(go)
@@ -405,7 +415,7 @@ def test_lookup_matches_corrblock_golden_and_oracle(ops, oracle):
         outs.append(s.view(B, H, W, -1))
     ref_out = torch.cat(outs, -1).permute(0, 3, 1, 2)
     ref_out.backward(go)
-    for lvl in range(3):   # level 3 is 1x2 here: grid_sample's (W-1) normalisation degenerates
+    for lvl in range(4 if pyr[3].shape[-2] > 1 else 3):   # level 3 is 1x2 at 12 x 16: grid_sample's (H-1) normalisation degenerates
         assert_close(pyr[lvl].grad, pyr2[lvl].grad, rtol=1e-4, atol_scale=1e-5, what=f"lookup grad level {lvl}")
 
 

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import assert_close, load_golden, t
+from closeness import assert_close
+from conftest import load_golden, t
 
 CORR_CASES = ["corr_check_defaults_f64", "corr_gradcheck_defaults_f64", "corr_flownetc_small_f32",
               "corr_pwc_small_f32", "corr_flownetc_ragged_f32", "corr_pwc_ragged_f32", "corr_rect_f32"]
@@ -89,20 +90,55 @@ def test_oracle_autograd_function_gradcheck(oracle):
     assert torch.autograd.gradcheck(f, (a, b))
 
 
-def test_lookup_and_altcorr_oracles_match_corrblock_golden(oracle):
+CORRBLOCK_CASES = ["raft_corrblock_lookup", "raft_corrblock_lookup_16x24"]
+CORRBLOCK_TOL = dict(rtol=1e-4, atol_scale=2e-6)
+
+
+def corrblock_level3(x):
+    """Channels 243..323 of a [B, 4 * 81, H, W] lookup at radius 4: the level-3 block."""
+    return x[:, 3 * 81:]
+
+
+def assert_matches_corrblock_golden(got, z, what):
+    """`got` against CorrBlock's stored output.  At 16 x 24 all 324 channels.  At 12 x 16 the reference's level 3 is 1 x 2 and its
+    grid_sample normalisation divides by H - 1 = 0 (models/raft/corr.py:47-63 through utils.bilinear_sampler): channels 243..323
+    of the golden are not finite -- the reference's artefact, asserted as a fact -- so levels 0-2 are compared, and the level-3
+    block of `got`, which the operators themselves compute from finite operands, has to be finite."""
+    gold = t(z["output"])
+    assert got.shape == gold.shape and gold.shape[1] == 4 * 81, f"{what}: shape {tuple(got.shape)} vs {tuple(gold.shape)}"
+    n = gold.shape[1]
+    if gold.shape[-2] >> 3 < 2:
+        n = 3 * 81
+        assert not bool(torch.isfinite(corrblock_level3(gold)).any()), f"{what}: the golden's level 3 at 12 x 16 is the reference's 0 / 0"
+        assert bool(torch.isfinite(corrblock_level3(got)).all()), f"{what}: level 3 is not finite"
+    assert_close(got[:, :n], gold[:, :n], what=what, **CORRBLOCK_TOL)
+
+
+@pytest.mark.parametrize("case", CORRBLOCK_CASES)
+def test_lookup_and_altcorr_oracles_match_corrblock_golden(oracle, case):
     """CorrBlock (models/raft/corr.py:26-106) pins the lookup restatement and, through the
-    all-pairs == on-the-fly identity, the alt_cuda_corr restatement."""
-    z = load_golden("raft_corrblock_lookup")
+    all-pairs == on-the-fly identity, the alt_cuda_corr restatement.
+
+    Two goldens (python tests/golden/make_golden.py raft_corr): 12 x 16, whose level-3 block the reference itself leaves non-finite
+    (see assert_matches_corrblock_golden), and 16 x 24 (B 2, C 32, radius 4, seed 22), finite throughout.  Measured here, the
+    oracles against the golden, worst element as a share of the bound 1e-4 |e| + 2e-6 max|e| (and max error / max |golden|):
+        12 x 16, channels 0..242:  lookup 0.31 (9.7e-7),  alt_corr 0.31 (1.09e-6)
+        16 x 24, channels 0..323:  lookup 0.31 (1.36e-6), alt_corr 0.45 (1.36e-6)
+    (under half of the bound, so seed 22 stays); on level 3 the two oracles differ by at most 0.04 of the bound in both cases.
+    A result of zeros fails every one of these comparisons (it passed the 12 x 16 ones while a NaN in the golden made every
+    bound NaN)."""
+    z = load_golden(case)
     f1, f2, coords = t(z["fmap1"]), t(z["fmap2"]), t(z["coords"])
     B, C, H, W = f1.shape
     corr = torch.matmul(f1.view(B, C, H * W).transpose(1, 2), f2.view(B, C, H * W)) / np.sqrt(C)
     pyr = [corr.view(B * H * W, 1, H, W)]
     for _ in range(3):
         pyr.append(torch.nn.functional.avg_pool2d(pyr[-1], 2, stride=2))
-    assert_close(pyr[0], t(z["level0"]), what="pyramid level 0")
+    if "level0" in z:
+        assert_close(pyr[0], t(z["level0"]), what="pyramid level 0")
     assert_close(pyr[3], t(z["level3"]), what="pyramid level 3")
     out = oracle.corr_lookup(pyr, coords, 4)
-    assert_close(out, t(z["output"]), rtol=1e-4, atol_scale=2e-6, what="lookup")
+    assert_matches_corrblock_golden(out, z, what=f"{case}: lookup")
     # alt_corr: pooled feature maps, coords/2^i, NHWC (corr.py:117-137)
     outs = []
     f2l = f2
@@ -114,7 +150,20 @@ def test_lookup_and_altcorr_oracles_match_corrblock_golden(oracle):
         if i < 3:
             f2l = torch.nn.functional.avg_pool2d(f2l, 2, stride=2)
     alt = torch.stack(outs, dim=1).reshape(B, -1, H, W) / np.sqrt(C)
-    assert_close(alt, t(z["output"]), rtol=1e-4, atol_scale=2e-6, what="alt_corr vs CorrBlock")
+    assert_matches_corrblock_golden(alt, z, what=f"{case}: alt_corr vs CorrBlock")
+    # the two operators agree on level 3 where the reference has nothing to say
+    assert_close(corrblock_level3(alt), corrblock_level3(out), what=f"{case}: level 3, alt_corr vs lookup", **CORRBLOCK_TOL)
+    # the hole itself: zeros must not pass, nor the golden's own NaN block, nor a NaN in any level of the result
+    with pytest.raises(AssertionError, match="elements off"):
+        assert_matches_corrblock_golden(torch.zeros_like(out), z, what=f"{case}: zeros")
+    if not bool(torch.isfinite(t(z["output"])).all()):
+        with pytest.raises(AssertionError, match="level 3 is not finite"):
+            assert_matches_corrblock_golden(t(z["output"]), z, what=f"{case}: the golden itself")
+    for i in range(4):
+        wrong = out.clone()
+        wrong[:, i * 81:(i + 1) * 81] = float("nan")
+        with pytest.raises(AssertionError, match="NaN|not finite"):
+            assert_matches_corrblock_golden(wrong, z, what=f"{case}: level {i} NaN")
 
 
 def test_altcorr_oracle_backward_is_adjoint(oracle):

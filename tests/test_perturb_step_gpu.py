@@ -223,7 +223,7 @@ def test_step_index_selects_a_new_row_at_each_graph_replay():
     torch.cuda.synchronize()
     assert int(step) == 1
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with L.graph_capture(graph):          # (no cyclic collection inside a capture: _lib.graph_capture)
         launches()
     step.zero_()
     for k, row in enumerate(rows + [(0, 0, 0, 0, 0)]):                      # the third replay is past the table: a copy

@@ -127,5 +127,6 @@ def test_train_sample_device_seeded_prefix_equals_recomputed(monkeypatch):
     assert steps and all(s.cone is not None for s in steps), "the windowed path must be the one compared"
     (pa, ma, sa), (pb, mb, sb) = outs
     assert sa == sb and torch.equal(ma, mb)
+    assert bool(torch.isfinite(pa).all()) and bool(torch.isfinite(pb).all()), "a patch is not finite"   # (NaN is never "differing" below)
     differing = float(((pa - pb).abs() > 1e-4 * 4.0).float().mean())         # updates saturate at +-2 per iteration
     assert differing <= 0.01, f"{differing:.2%} of the patch pixels differ"

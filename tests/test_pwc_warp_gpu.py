@@ -4,7 +4,7 @@ validity mask, both gradients; flows that leave the frame, ragged sizes, a 1-pix
 import pytest
 import torch
 
-from conftest import assert_close
+from closeness import assert_close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -4,7 +4,8 @@ frame sides that are multiples of 8 only, the precision switch's cache key and t
 import pytest
 import torch
 
-from conftest import assert_close, t
+from closeness import assert_close
+from conftest import t
 from raft_fnc_helpers import check_encoder, check_weights, encoder_case, encoder_heads, fetch, model_golden
 
 pytestmark = pytest.mark.gpu

@@ -4,7 +4,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import assert_close
+from closeness import assert_close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

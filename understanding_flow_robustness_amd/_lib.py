@@ -407,6 +407,37 @@ def stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class graph_capture:
+    """`torch.cuda.graph(graph)` with Python's cyclic collector out of the way.  A dead reference cycle that holds a
+    `torch.cuda.CUDAGraph` (the step of an earlier call) is destroyed whenever the collector happens to run; `~CUDAGraph` calls into
+    HIP, which is not permitted while a stream is capturing, and the exception it throws from a destructor ends the process.  torch
+    used to collect in `torch.cuda.graph.__enter__` and no longer does (2.9 on), so: collect BEFORE the capture begins, and let no
+    collection run inside it (a capture of a whole forward and backward allocates enough objects to trigger one)."""
+
+    def __init__(self, graph, **kwargs):
+        self._ctx = torch.cuda.graph(graph, **kwargs)
+
+    def __enter__(self):
+        import gc
+        gc.collect()
+        self._gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            return self._ctx.__enter__()
+        except BaseException:
+            if self._gc_was_on:
+                gc.enable()
+            raise
+
+    def __exit__(self, *exc):
+        import gc
+        try:
+            return self._ctx.__exit__(*exc)
+        finally:
+            if self._gc_was_on:
+                gc.enable()
+
+
 def dtype_code(t: torch.Tensor) -> int:
     if t.dtype == torch.float32:
         return UFR_F32

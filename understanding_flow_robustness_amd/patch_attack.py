@@ -525,12 +525,12 @@ class PatchAttackStep:
                 graphs[True] = graphs[False]
                 break
             ga = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga):
+            with L.graph_capture(ga):
                 self._part_a()
             gb = None
             if self.world > 1:
                 gb = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gb):
+                with L.graph_capture(gb):
                     self._part_b()
             graphs[later] = (ga, gb)
         self._set_later(False)

@@ -179,12 +179,12 @@ class UniversalPerturbationStep:
         torch.cuda.synchronize(self.dev)
         if self.use_graph:
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with L.graph_capture(graph):
                 self._part_a()
             graph_b = None
             if self.world > 1:
                 graph_b = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph_b):
+                with L.graph_capture(graph_b):
                     self._update(None, None, 2)
             self.graph, self.graph_b = graph, graph_b
         self._captured = True

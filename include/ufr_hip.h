@@ -1053,6 +1053,46 @@ int ufr_sweep_metrics(const float* pred, const float* gt, const float* mask_p, c
                       int H, int W, int Hg, int Wg, int ph, int pw, int valid_in_patch, double* ws, long ws_elems, float* out,
                       int row0, int rows, ufr_stream_t stream);
 
+/* ---- patch evaluation over a validation set (csrc/patch_eval.hip) -------------------------------------------------------------
+ * patch_attacks/test_patch.py:242-466 evaluates a finished (or hand-crafted) patch on every item of a validation set; with
+ * `--different_pos` the patch moves, turns and scales between the two frames.  K items of a chunk, each with its OWN frames and
+ * ground truth, are served by two entries.  A placement is a record in patch coordinates, padded to a slot of fixed size
+ * sh x sw with mask 0 (and patch / flow 0): patch and mask slots are float32 [K,3,sh,sw], the flow slot is float32 [K,3,sh,sw]
+ * = (u, v, valid) of the patch's own motion, already multiplied by the first-frame mask.  places[k] = (y_tgt, x_tgt, h_tgt,
+ * w_tgt, y_ref, x_ref, h_ref, w_ref), int32 [K,8] on the device, and `places_host`, the same table on the host, is REQUIRED:
+ * every record is checked (1 <= h <= sh, 1 <= w <= sw, 0 <= y, y + h <= H, 0 <= x, x + w <= W) before any launch.  The
+ * second four are read only when a second-frame record is given.
+ *
+ * ufr_eval_paste: tgt / ref [K,3,H,W] -> adv_tgt = clamp((1 - M_tgt) * tgt + M_tgt * P_tgt, lo, hi) and adv_ref likewise with the
+ *   second-frame record (p_ref / m_ref; both NULL: both frames take the first record), the arithmetic and rounding order of
+ *   ufr_patch_paste_placed with do_clamp = 1.  One launch; 16-byte accesses when W % 4 == 0 and the frame pointers are 16-byte
+ *   aligned.
+ * ufr_eval_metrics: pred_clean / pred_adv [K,2,H,W], gt [K,3,Hg,Wg] -> out[row0 + k] = (epe, adv_epe, cos_sim, adv_cos_sim),
+ *   float32 quadruples of a result buffer of `rows` rows.  For every ground-truth pixel, in one pass and in float64:
+ *     p, q   = pred_clean_k, pred_adv_k resized bilinearly, align_corners = False (the rule of ufr_sweep_metrics);
+ *     mt, mr = the canvas masks of the two records resized the same way, channel for channel (mr = 0 when m_ref == NULL);
+ *     gt'    = (1 - mr) * gt                                                              (test_patch.py:430-446)
+ *     f      = (0, 0, 1), or (0, 0, 0) when ignore_mask_flow != 0, or -- when `flow` is given, whatever the flag says
+ *              (:420-453) -- the canvas flow (the flow slot at (y_tgt, x_tgt), 0 elsewhere) resized by scipy.ndimage.zoom's
+ *              order-1 rule: source = dst * ((H - 1) / (Hg - 1)), floor + linear weights, 0 for a source below 0 or above H - 1;
+ *     g      = (1 - mt) * gt' + mt * f                                                    (:455-457)
+ *   and the end-point error and cosine similarity of ufr_sweep_metrics for (gt', p) and (g, q), each weighted by its own valid
+ *   channel and divided by sum(valid) + 1e-8.  The clean metrics use gt' too, like the reference, which overwrites its ground
+ *   truth before it computes them.  Workgroup partials in `ws` (ufr_eval_metrics_workspace_doubles(K) doubles) are added in a
+ *   fixed order by a second launch: no float atomics, two runs are bit-identical.  Neither canvases nor resized masks nor g
+ *   are written to memory.
+ * Refused (UFR_EINVAL + ufr_last_error) before any launch: null pointers (a second-frame patch without its mask or the reverse),
+ *   K < 1, non-positive sizes, a slot larger than the frame, a record that is larger than its slot or leaves the frame, lo > hi,
+ *   an ignore flag other than 0 / 1, rows outside the result buffer, a workspace that is too small.  (scipy's zoom by Hg / H writes
+ *   round(H * (Hg / H)) samples, which is Hg for every pair of int sizes: two roundings cannot move the product by 0.5.) */
+int ufr_eval_paste(const float* tgt, const float* ref, const float* p_tgt, const float* m_tgt, const float* p_ref, const float* m_ref,
+                   const int* places, const int* places_host, float* adv_tgt, float* adv_ref, int K, int H, int W, int sh, int sw,
+                   float lo, float hi, ufr_stream_t stream);
+long ufr_eval_metrics_workspace_doubles(int K);   /* -1 when K < 1 */
+int ufr_eval_metrics(const float* pred_clean, const float* pred_adv, const float* gt, const float* m_tgt, const float* m_ref,
+                     const float* flow, const int* places, const int* places_host, int K, int H, int W, int Hg, int Wg, int sh,
+                     int sw, int ignore_mask_flow, double* ws, long ws_elems, float* out, int row0, int rows, ufr_stream_t stream);
+
 /* ---- feature-map statistics (csrc/feature_stats.hip) -------------------------------------------------------------------------
  * patch_attacks/test_patch_embeddings.py takes np.mean over the pixels of every feature map of a forward; here the maps stay where
  * the engine left them and only their per-image, per-channel SUMS leave the device, all segments of a forward in one result matrix.

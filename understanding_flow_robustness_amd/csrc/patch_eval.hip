@@ -1,0 +1,295 @@
+// patch_eval.hip -- the evaluation loop of patch_attacks/test_patch.py:242-466 (gfx950): a finished or hand-crafted patch is placed
+// on every item of a validation set -- with `--different_pos` at another place, angle and scale in the second frame -- and the
+// end-point error / cosine similarity of the clean and the attacked prediction are recorded per item.  Two streaming entries serve a
+// chunk of K items, each with its own frames, ground truth and placement record (a slot in patch coordinates, include/ufr_hip.h):
+//   ufr_eval_paste    the K adversarial pairs, one launch;
+//   ufr_eval_metrics  resized predictions, resized canvas masks of both records, the occlusion of the ground truth by the second
+//                     record, the patch's own flow resized by scipy's zoom rule, the blend and all four metrics in one pass over the
+//                     ground-truth pixels; float64 throughout, workgroup partials + a finalize launch (the pattern of
+//                     patch_sweep.hip and train_loss.hip): no float atomics, two runs are bit-identical.
+// The reference does, per item: six canvas-sized host arrays and a canvas-sized flow, five H2D copies, ten torch operators for the
+// pastes, two bilinear resizes, a scipy.ndimage.zoom of the canvas flow on the host, ten operators for the blends and four metric
+// calls that each end in `.item()`.
+#include <cstdint>
+
+#include "ufr_common.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kSlots = 128;            // workgroups (= partials) per item at most
+constexpr int kSums = 6;               // clean: valid * epe, valid * cos, valid; attacked: the same three
+constexpr int kPlace = 8;              // places[k] = {y_tgt, x_tgt, h_tgt, w_tgt, y_ref, x_ref, h_ref, w_ref}
+
+using ufr::dev::bilinear;
+using ufr::dev::bilinear_source;
+using ufr::dev::block_sum;
+using ufr::dev::paste_clamped;
+
+// idx runs over [K,3,H,W] in units of V floats; the first frame takes record 0 of its item, the second frame record `second`
+template <int V>
+__global__ __launch_bounds__(kBlock) void eval_paste_kernel(const float* __restrict__ tgt, const float* __restrict__ ref,
+                                                            const float* __restrict__ p_tgt, const float* __restrict__ m_tgt,
+                                                            const float* __restrict__ p_ref, const float* __restrict__ m_ref,
+                                                            const int* __restrict__ places, int second, float* __restrict__ adv_tgt,
+                                                            float* __restrict__ adv_ref, long total, int H, int W, int sh, int sw,
+                                                            float lo, float hi) {
+  const long HW = (long)H * W, CHW = 3 * HW;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+    const long idx = q * V;
+    const int k = (int)(idx / CHW);
+    const long src = idx - (long)k * CHW;
+    const int c = (int)(src / HW);
+    const long pix = src - (long)c * HW;
+    const int y = (int)(pix / W), x = (int)(pix - (long)y * W);
+    const int* __restrict__ pl = places + (long)k * kPlace;
+    const int* __restrict__ pr = pl + 4 * second;
+    const int it = y - pl[0], jt0 = x - pl[1], ht = pl[2], wt = pl[3];
+    const int ir = y - pr[0], jr0 = x - pr[1], hr = pr[2], wr = pr[3];
+    const long slot = ((long)k * 3 + c) * sh * sw;
+    float t[V], r[V];
+    if constexpr (V == 4) {
+      const float4 tv = *reinterpret_cast<const float4*>(tgt + idx), rv = *reinterpret_cast<const float4*>(ref + idx);
+      t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+      r[0] = rv.x; r[1] = rv.y; r[2] = rv.z; r[3] = rv.w;
+    } else {
+      t[0] = tgt[idx];
+      r[0] = ref[idx];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const int jt = jt0 + v, jr = jr0 + v;
+      float m = 0.f, pv = 0.f;
+      if ((unsigned)it < (unsigned)ht && (unsigned)jt < (unsigned)wt) {
+        const long e = slot + (long)it * sw + jt;
+        m = m_tgt[e];
+        pv = p_tgt[e];
+      }
+      t[v] = paste_clamped(t[v], m, pv, lo, hi);
+      m = 0.f; pv = 0.f;
+      if ((unsigned)ir < (unsigned)hr && (unsigned)jr < (unsigned)wr) {
+        const long e = slot + (long)ir * sw + jr;
+        m = m_ref[e];
+        pv = p_ref[e];
+      }
+      r[v] = paste_clamped(r[v], m, pv, lo, hi);
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(adv_tgt + idx) = make_float4(t[0], t[1], t[2], t[3]);
+      *reinterpret_cast<float4*>(adv_ref + idx) = make_float4(r[0], r[1], r[2], r[3]);
+    } else {
+      adv_tgt[idx] = t[0];
+      adv_ref[idx] = r[0];
+    }
+  }
+}
+
+// ---- metrics ------------------------------------------------------------------------------------------------------------------
+// a record's canvas at frame rows y0 / y1 and columns x0 / x1 (already inside the frame): the slot inside the h x w rectangle at
+// (oy, ox), 0 outside
+struct Corners {
+  int i0, i1, j0, j1;
+  bool a0, a1, b0, b1, any;
+};
+
+__device__ __forceinline__ Corners corners(int y0, int y1, int x0, int x1, int oy, int ox, int h, int w) {
+  Corners q;
+  q.i0 = y0 - oy; q.i1 = y1 - oy; q.j0 = x0 - ox; q.j1 = x1 - ox;
+  q.a0 = (unsigned)q.i0 < (unsigned)h; q.a1 = (unsigned)q.i1 < (unsigned)h;
+  q.b0 = (unsigned)q.j0 < (unsigned)w; q.b1 = (unsigned)q.j1 < (unsigned)w;
+  q.any = (q.a0 || q.a1) && (q.b0 || q.b1);
+  return q;
+}
+
+__device__ __forceinline__ double resized_canvas(const float* __restrict__ s, int sw, const Corners& q, double ly, double lx) {
+  const double v00 = q.a0 && q.b0 ? (double)s[q.i0 * sw + q.j0] : 0.0, v01 = q.a0 && q.b1 ? (double)s[q.i0 * sw + q.j1] : 0.0;
+  const double v10 = q.a1 && q.b0 ? (double)s[q.i1 * sw + q.j0] : 0.0, v11 = q.a1 && q.b1 ? (double)s[q.i1 * sw + q.j1] : 0.0;
+  return bilinear(v00, v01, v10, v11, ly, lx);
+}
+
+// losses.py:8-50 for one pixel: the end-point error against the rescaled prediction and torch's cosine_similarity
+__device__ __forceinline__ void pixel_metrics(const double g[3], double fu, double fv, double scale_u, double scale_v, double* sum) {
+  const double du = g[0] - fu * scale_u, dv = g[1] - fv * scale_v;
+  const double epe = sqrt(du * du + dv * dv);
+  const double ng = fmax(sqrt(g[0] * g[0] + g[1] * g[1]), 1e-8), nf = fmax(sqrt(fu * fu + fv * fv), 1e-8);
+  const double cs = (g[0] / ng) * (fu / nf) + (g[1] / ng) * (fv / nf);
+  sum[0] += epe * g[2];
+  sum[1] += cs * g[2];
+  sum[2] += g[2];
+}
+
+// grid (slots, K): workgroup (s, k) walks the ground-truth pixels s * 256 + t, + slots * 256, ... of item k
+// patch_flow: 0 = (0, 0, 0), 1 = (0, 0, 1), 2 = the flow slot; zy / zx: scipy's zoom factors (H - 1) / (Hg - 1), (W - 1) / (Wg - 1)
+__global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __restrict__ pred_clean, const float* __restrict__ pred_adv,
+                                                              const float* __restrict__ gt, const float* __restrict__ m_tgt,
+                                                              const float* __restrict__ m_ref, const float* __restrict__ flow,
+                                                              const int* __restrict__ places, int H, int W, int Hg, int Wg, int sh,
+                                                              int sw, int patch_flow, double zy, double zx, double* __restrict__ part) {
+  __shared__ double lds[kBlock / 64];
+  const int k = blockIdx.y;
+  const long HW = (long)H * W, HWg = (long)Hg * Wg;
+  const int plane = sh * sw;
+  const float* __restrict__ cu = pred_clean + (long)k * 2 * HW;
+  const float* __restrict__ cv = cu + HW;
+  const float* __restrict__ au = pred_adv + (long)k * 2 * HW;
+  const float* __restrict__ av = au + HW;
+  const float* __restrict__ gk = gt + (long)k * 3 * HWg;
+  const float* __restrict__ mt = m_tgt + (long)k * 3 * plane;
+  const float* __restrict__ mr = m_ref != nullptr ? m_ref + (long)k * 3 * plane : nullptr;
+  const float* __restrict__ fl = flow != nullptr ? flow + (long)k * 3 * plane : nullptr;
+  const int* __restrict__ pl = places + (long)k * kPlace;
+  const int yt = pl[0], xt = pl[1], ht = pl[2], wt = pl[3];
+  int yr = 0, xr = 0, hr = 0, wr = 0;
+  if (mr != nullptr) { yr = pl[4]; xr = pl[5]; hr = pl[6]; wr = pl[7]; }
+  const double sy = (double)H / (double)Hg, sx = (double)W / (double)Wg;
+  const double scale_u = (double)Wg / (double)W, scale_v = (double)Hg / (double)H;     // losses.py:27
+  double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
+    const int yg = (int)(p / Wg), xg = (int)(p - (long)yg * Wg);
+    int y0, y1, x0, x1;
+    double ly, lx;
+    bilinear_source(yg, sy, H, y0, y1, ly);
+    bilinear_source(xg, sx, W, x0, x1, lx);
+    const long r0 = (long)y0 * W, r1 = (long)y1 * W;
+    const double pu = bilinear((double)cu[r0 + x0], (double)cu[r0 + x1], (double)cu[r1 + x0], (double)cu[r1 + x1], ly, lx);
+    const double pv = bilinear((double)cv[r0 + x0], (double)cv[r0 + x1], (double)cv[r1 + x0], (double)cv[r1 + x1], ly, lx);
+    const double qu = bilinear((double)au[r0 + x0], (double)au[r0 + x1], (double)au[r1 + x0], (double)au[r1 + x1], ly, lx);
+    const double qv = bilinear((double)av[r0 + x0], (double)av[r0 + x1], (double)av[r1 + x0], (double)av[r1 + x1], ly, lx);
+    double g[3] = {(double)gk[p], (double)gk[HWg + p], (double)gk[2 * HWg + p]};
+    if (mr != nullptr) {                                                          // test_patch.py:430-446: occluded by the moved patch
+      const Corners q = corners(y0, y1, x0, x1, yr, xr, hr, wr);
+      if (q.any) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[c] = (1.0 - resized_canvas(mr + c * plane, sw, q, ly, lx)) * g[c];
+      }
+    }
+    double ga[3] = {g[0], g[1], g[2]};
+    const Corners q = corners(y0, y1, x0, x1, yt, xt, ht, wt);
+    if (q.any) {
+      double f[3] = {0.0, 0.0, patch_flow == 1 ? 1.0 : 0.0};
+      if (patch_flow == 2) {
+        // scipy.ndimage.zoom, order 1, mode='constant' (placement.hip): a source outside [0, n - 1] on either axis gives 0
+        const double cy = zy * (double)yg, cx = zx * (double)xg;
+        if (!(cy < 0.0 || cy > (double)(H - 1) || cx < 0.0 || cx > (double)(W - 1))) {
+          const int fy0 = (int)floor(cy), fx0 = (int)floor(cx);
+          const double ty = cy - (double)fy0, tx = cx - (double)fx0;
+          const int fy1 = fy0 + 1 < H ? fy0 + 1 : fy0, fx1 = fx0 + 1 < W ? fx0 + 1 : fx0;
+          const double wy1 = fy0 + 1 < H ? ty : 0.0, wx1 = fx0 + 1 < W ? tx : 0.0, wy0 = 1.0 - ty, wx0 = 1.0 - tx;
+          const Corners z = corners(fy0, fy1, fx0, fx1, yt, xt, ht, wt);
+          if (z.any) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float* __restrict__ s = fl + c * plane;
+              double v = (z.a0 && z.b0 ? (double)s[z.i0 * sw + z.j0] : 0.0) * (wy0 * wx0);
+              v += (z.a0 && z.b1 ? (double)s[z.i0 * sw + z.j1] : 0.0) * (wy0 * wx1);
+              v += (z.a1 && z.b0 ? (double)s[z.i1 * sw + z.j0] : 0.0) * (wy1 * wx0);
+              v += (z.a1 && z.b1 ? (double)s[z.i1 * sw + z.j1] : 0.0) * (wy1 * wx1);
+              f[c] = v;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double m = resized_canvas(mt + c * plane, sw, q, ly, lx);
+        ga[c] = (1.0 - m) * g[c] + m * f[c];                                      // test_patch.py:455-457
+      }
+    }
+    pixel_metrics(g, pu, pv, scale_u, scale_v, sum);
+    pixel_metrics(ga, qu, qv, scale_u, scale_v, sum + 3);
+  }
+  for (int q = 0; q < kSums; ++q) {
+    const double t = block_sum<kBlock>(sum[q], lds);
+    if (threadIdx.x == 0) part[((long)k * kSlots + blockIdx.x) * kSums + q] = t;
+  }
+}
+
+// grid K: one workgroup adds the `slots` partials of its item in a fixed order
+__global__ __launch_bounds__(kBlock) void eval_metrics_finalize_kernel(const double* __restrict__ part, int slots,
+                                                                       float* __restrict__ out) {
+  __shared__ double lds[kBlock / 64];
+  const int k = blockIdx.x;
+  double t[kSums];
+  for (int q = 0; q < kSums; ++q)
+    t[q] = block_sum<kBlock>((int)threadIdx.x < slots ? part[((long)k * kSlots + threadIdx.x) * kSums + q] : 0.0, lds);
+  if (threadIdx.x == 0) {
+    const double den = t[2] + 1e-8, den_adv = t[5] + 1e-8;                        // losses.py:22
+    out[4 * k] = (float)(t[0] / den);                                             // epe, adv_epe, cos_sim, adv_cos_sim
+    out[4 * k + 1] = (float)(t[3] / den_adv);
+    out[4 * k + 2] = (float)(t[1] / den);
+    out[4 * k + 3] = (float)(t[4] / den_adv);
+  }
+}
+
+int check_places(const char* what, const int* places_host, int K, int records, int H, int W, int sh, int sw) {
+  for (int k = 0; k < K; ++k)
+    for (int r = 0; r < records; ++r) {
+      const int* p = places_host + (long)k * kPlace + 4 * r;
+      UFR_REQUIRE(p[2] >= 1 && p[2] <= sh && p[3] >= 1 && p[3] <= sw, "%s: item %d, frame %d: the %dx%d record does not fit its %dx%d slot",
+                  what, k, r, p[2], p[3], sh, sw);
+      UFR_REQUIRE(p[0] >= 0 && p[0] <= H - p[2] && p[1] >= 0 && p[1] <= W - p[3],
+                  "%s: item %d, frame %d: placement (%d, %d) of the %dx%d patch leaves the %dx%d frame", what, k, r, p[0], p[1], p[2],
+                  p[3], H, W);
+    }
+  return UFR_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int ufr_eval_paste(const float* tgt, const float* ref, const float* p_tgt, const float* m_tgt, const float* p_ref,
+                              const float* m_ref, const int* places, const int* places_host, float* adv_tgt, float* adv_ref, int K,
+                              int H, int W, int sh, int sw, float lo, float hi, ufr_stream_t stream) {
+  UFR_REQUIRE(tgt && ref && p_tgt && m_tgt && places && adv_tgt && adv_ref, "eval paste: null pointer argument");
+  UFR_REQUIRE(places_host, "eval paste: the placements are needed on the host too (every record is checked before the launch)");
+  UFR_REQUIRE((p_ref == nullptr) == (m_ref == nullptr), "eval paste: null pointer argument (a second-frame record is a patch AND a mask)");
+  UFR_REQUIRE(K > 0 && H > 0 && W > 0 && sh > 0 && sw > 0, "eval paste: bad shape K=%d H=%d W=%d sh=%d sw=%d", K, H, W, sh, sw);
+  UFR_REQUIRE(sh <= H && sw <= W, "eval paste: the %dx%d slot is larger than the %dx%d frame", sh, sw, H, W);
+  UFR_REQUIRE((long)K * 3 * H * W < (1L << 40) && (long)K * 3 * sh * sw < (1L << 30), "eval paste: too many pixels");
+  UFR_REQUIRE(lo <= hi, "eval paste: empty pixel range [%g, %g]", (double)lo, (double)hi);
+  const int second = p_ref != nullptr ? 1 : 0;
+  if (int rc = check_places("eval paste", places_host, K, 1 + second, H, W, sh, sw)) return rc;
+  if (!second) { p_ref = p_tgt; m_ref = m_tgt; }
+  hipStream_t st = ufr::as_stream(stream);
+  const long total = (long)K * 3 * H * W;
+  if (W % 4 == 0 && aligned16(tgt) && aligned16(ref) && aligned16(adv_tgt) && aligned16(adv_ref))
+    eval_paste_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(tgt, ref, p_tgt, m_tgt, p_ref, m_ref, places, second,
+                                                                               adv_tgt, adv_ref, total / 4, H, W, sh, sw, lo, hi);
+  else
+    eval_paste_kernel<1><<<ufr::stream_grid(total, kBlock), kBlock, 0, st>>>(tgt, ref, p_tgt, m_tgt, p_ref, m_ref, places, second,
+                                                                           adv_tgt, adv_ref, total, H, W, sh, sw, lo, hi);
+  return ufr::launched("eval_paste_kernel");
+}
+
+extern "C" long ufr_eval_metrics_workspace_doubles(int K) { return K < 1 ? -1 : (long)K * kSlots * kSums; }
+
+extern "C" int ufr_eval_metrics(const float* pred_clean, const float* pred_adv, const float* gt, const float* m_tgt, const float* m_ref,
+                                const float* flow, const int* places, const int* places_host, int K, int H, int W, int Hg, int Wg,
+                                int sh, int sw, int ignore_mask_flow, double* ws, long ws_elems, float* out, int row0, int rows,
+                                ufr_stream_t stream) {
+  UFR_REQUIRE(pred_clean && pred_adv && gt && m_tgt && places && ws && out, "eval metrics: null pointer argument");
+  UFR_REQUIRE(places_host, "eval metrics: the placements are needed on the host too (every record is checked before the launch)");
+  UFR_REQUIRE(K > 0 && K <= 65535 && H > 0 && W > 0 && Hg > 0 && Wg > 0 && sh > 0 && sw > 0,
+              "eval metrics: bad shape K=%d H=%d W=%d Hg=%d Wg=%d sh=%d sw=%d", K, H, W, Hg, Wg, sh, sw);
+  UFR_REQUIRE(sh <= H && sw <= W, "eval metrics: the %dx%d slot is larger than the %dx%d frame", sh, sw, H, W);
+  UFR_REQUIRE((long)H * W < (1L << 30) && (long)Hg * Wg < (1L << 30) && (long)K * 3 * sh * sw < (1L << 30),
+              "eval metrics: too many pixels");
+  UFR_REQUIRE(ignore_mask_flow == 0 || ignore_mask_flow == 1, "eval metrics: ignore_mask_flow = %d (0 or 1)", ignore_mask_flow);
+  UFR_REQUIRE(row0 >= 0 && rows > 0 && (long)row0 + K <= rows, "eval metrics: rows %d .. %ld leave the result buffer of %d rows", row0,
+              (long)row0 + K - 1, rows);
+  UFR_REQUIRE(ws_elems >= ufr_eval_metrics_workspace_doubles(K), "eval metrics: workspace of %ld doubles, %ld needed", ws_elems,
+              ufr_eval_metrics_workspace_doubles(K));
+  if (int rc = check_places("eval metrics", places_host, K, m_ref != nullptr ? 2 : 1, H, W, sh, sw)) return rc;
+  hipStream_t st = ufr::as_stream(stream);
+  const long npix = (long)Hg * Wg;
+  int slots = ufr::ceil_div(npix, kBlock);
+  if (slots > kSlots) slots = kSlots;
+  const int patch_flow = flow != nullptr ? 2 : (ignore_mask_flow ? 0 : 1);
+  const double zy = Hg > 1 ? (double)(H - 1) / (double)(Hg - 1) : 1.0, zx = Wg > 1 ? (double)(W - 1) / (double)(Wg - 1) : 1.0;
+  eval_metrics_kernel<<<dim3(slots, K), kBlock, 0, st>>>(pred_clean, pred_adv, gt, m_tgt, m_ref, flow, places, H, W, Hg, Wg, sh, sw,
+                                                         patch_flow, zy, zx, ws);
+  if (int rc = ufr::launched("eval_metrics_kernel")) return rc;
+  eval_metrics_finalize_kernel<<<K, kBlock, 0, st>>>(ws, slots, out + 4L * row0);
+  return ufr::launched("eval_metrics_finalize_kernel");
+}

@@ -20,14 +20,8 @@ constexpr int kSlots = 128;            // workgroups (= partials) per position a
 constexpr int kSums = 3;               // valid * epe, valid * cos, valid
 constexpr int kWinInts = 8;            // win[k] = {y0, x0, need_h, need_w, ymin, ymax, xmin, xmax} (window.hip)
 
-using ufr::dev::clampf;
 using ufr::dev::cone_axis;
-
-// attack.hip's paste_placed_kernel, do_clamp = 1: (1-m)*img and m*patch are rounded separately, then added (no fma)
-__device__ __forceinline__ float paste_clamped(float img, float m, float pv, float lo, float hi) {
-  const float mp = m * pv, om = 1.0f - m;
-  return clampf(om * img + mp, lo, hi);
-}
+using ufr::dev::paste_clamped;      // attack.hip's paste_placed_kernel, do_clamp = 1
 
 // ---- canvas form: idx runs over [K,3,H,W] in units of V floats; the clean pair is [3,H,W] ---------------------------------------
 template <int V>
@@ -171,20 +165,8 @@ __global__ __launch_bounds__(kBlock) void sweep_paste_window_kernel(const float*
 // ---- metrics ------------------------------------------------------------------------------------------------------------------
 using ufr::dev::block_sum;          // the sum over the workgroup in a fixed order, returned to every thread
 
-// torch's upsample_bilinear2d, align_corners = False, size given (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index):
-//   src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out;  i0 = (int)src;  i1 = i0 + (i0 < in - 1);  l1 = src - i0
-// in float64: with in == out the source is dst itself and l1 = 0
-__device__ __forceinline__ void bilinear_source(int dst, double scale, int in, int& i0, int& i1, double& l1) {
-  const double src = fmax(scale * ((double)dst + 0.5) - 0.5, 0.0);
-  i0 = min((int)src, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = src - (double)i0;
-}
-
-__device__ __forceinline__ double bilinear(double v00, double v01, double v10, double v11, double ly, double lx) {
-  const double hy = 1.0 - ly, hx = 1.0 - lx;
-  return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
-}
+using ufr::dev::bilinear;           // torch's upsample_bilinear2d, align_corners = False, in float64
+using ufr::dev::bilinear_source;
 
 // grid (slots, K): workgroup (s, k) walks the ground-truth pixels s * 256 + t, + slots * 256, ... of position k
 __global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,

@@ -157,6 +157,28 @@ __device__ inline double block_sum(double v, double* lds) {
   return t;
 }
 
+// ---- shared by patch_sweep.hip and patch_eval.hip ---------------------------------------------------------------------------------
+// attack.hip's paste_placed_kernel, do_clamp = 1: (1-m)*img and m*patch are rounded separately, then added (no fma)
+__device__ __forceinline__ float paste_clamped(float img, float m, float pv, float lo, float hi) {
+  const float mp = m * pv, om = 1.0f - m;
+  return clampf(om * img + mp, lo, hi);
+}
+
+// torch's upsample_bilinear2d, align_corners = False, size given (aten/src/ATen/native/UpSample.h area_pixel_compute_source_index):
+//   src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out;  i0 = (int)src;  i1 = i0 + (i0 < in - 1);  l1 = src - i0
+// in float64: with in == out the source is dst itself and l1 = 0
+__device__ __forceinline__ void bilinear_source(int dst, double scale, int in, int& i0, int& i1, double& l1) {
+  const double src = fmax(scale * ((double)dst + 0.5) - 0.5, 0.0);
+  i0 = min((int)src, in - 1);
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = src - (double)i0;
+}
+
+__device__ __forceinline__ double bilinear(double v00, double v01, double v10, double v11, double ly, double lx) {
+  const double hy = 1.0 - ly, hx = 1.0 - lx;
+  return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
 }  // namespace dev
 }  // namespace ufr
 

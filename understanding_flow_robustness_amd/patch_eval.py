@@ -1,0 +1,205 @@
+"""The patch evaluation of the paper's tables (patch_attacks/test_patch.py:242-466): a finished patch, a random patch or a
+hand-crafted self-similar pattern (`utils_patch.get_patch_and_mask`) is placed on every item of a validation set and the end-point
+error / cosine similarity of the clean and the attacked prediction are recorded per item.  With `--different_pos` the patch moves,
+turns and scales between the two frames, the ground truth it covers in the second frame is dropped and the ground truth inside
+the patch becomes the patch's own motion.
+
+Reference, per item: a canvas-sized host placement (six canvases and a flow field), five H2D copies, two batch-1 forwards, ten
+torch operators for the pastes, two mask resizes, a `scipy.ndimage.zoom` of the canvas-sized flow on the host, ten operators for the
+blends and four metric calls that each end in `.item()`.  Here the placement of every item is drawn in loader order (so the
+`np.random` stream does not depend on `chunk`) as a record in patch coordinates (patch_transform.PlacementRecord), up to `chunk`
+consecutive items of equal size are stacked, and per chunk
+
+    ufr_eval_paste (csrc/patch_eval.hip)  ->  ONE forward of the 2K clean and pasted pairs  ->  ufr_eval_metrics
+
+run; the host reads the results once, at the end.
+"""
+from __future__ import annotations
+
+from argparse import Namespace
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+
+@dataclass
+class EvalResult:
+    per_item: np.ndarray         # float64 [N,4] in the order of `error_names`
+    mean: np.ndarray             # float64 [4]: the plain mean over items (what the script's AverageMeter reports)
+    locations: list              # per item [(x_tgt, y_tgt), (x_ref, y_ref)]
+    error_names: list
+
+
+def _refuse_3d(what):
+    raise NotImplementedError(f"{what}: the reference projects the patch into the 3-D scene (project_patch_3d_scene, from depth, "
+                              "calibration and poses); that projection is not part of this project")
+
+
+class _Evaluation:
+    """The state of one call: the float64 patch state, the items waiting for their chunk, the results."""
+
+    def __init__(self, flow_net, patch, mask, patch_shape, args, chunk):
+        from .patch_attack import _pixel_range
+        self.net, self.args, self.chunk = flow_net, args, int(chunk)
+        self.patch, self.mask, self.patch_shape = patch, mask, tuple(patch_shape)
+        self.patch_d = self.mask_d = None
+        self.lo, self.hi = _pixel_range(args.flownet)
+        self.different = bool(getattr(args, "different_pos", False))
+        self.homogeneous = bool(getattr(args, "HOMOGENUOUS", False))
+        self.norotate = bool(getattr(args, "norotate", False))
+        self.ignore = 1 if getattr(args, "ignore_mask_flow", False) else 0
+        self.square = getattr(args, "patch_type", "circle") == "square"
+        self.fixed_loc = (int(getattr(args, "fixed_loc_x", -1)), int(getattr(args, "fixed_loc_y", -1)))
+        self.waiting, self.results, self.locations = [], [], []
+        self.ws = None
+        self.events = None               # tools/bench_patch_eval.py: device events around the two entries
+
+    def _mark(self, stage):
+        if self.events is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.events.append((stage, ev))
+
+    def _state(self, dev):
+        if self.patch_d is None:
+            f64 = lambda a: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, torch.float64)
+            self.patch_d, self.mask_d = f64(self.patch).contiguous(), f64(self.mask).contiguous()
+        return self.patch_d, self.mask_d
+
+    def place(self, data_shape, margin, dev):
+        """test_patch.py:279-361: one item's placement record; `np.random` is consumed exactly as the script's transform does."""
+        from . import patch_transform as pt
+        patch_d, mask_d = self._state(dev)
+        if self.different:                                       # whatever the patch type, like the script
+            rec = pt.circle_transform_different_device(patch_d, mask_d, patch_d, data_shape, self.patch_shape, margin,
+                                                       norotate=self.norotate, fixed_loc=self.fixed_loc)
+            self.locations.append([(rec.origin_tgt[1], rec.origin_tgt[0]), (rec.origin_ref[1], rec.origin_ref[0])])
+            return rec
+        if self.square:
+            cp, cm, _, x, y, (self.patch_d, self.mask_d, _) = pt.square_transform_device(patch_d, mask_d, patch_d, data_shape,
+                                                                                         self.patch_shape, norotate=self.norotate)
+            shape, slot = self.patch_d.shape, int(max(self.patch_d.shape[-2:]))
+        else:
+            cp, cm, _, x, y, shape = pt.circle_transform_device(patch_d, mask_d, patch_d, data_shape, self.patch_shape, margin,
+                                                                norotate=self.norotate, fixed_loc=self.fixed_loc)
+            slot = pt.slot_side(max(patch_d.shape[-2:]))
+        self.locations.append([(x, y), (x, y)])
+        return pt.record_from_canvas(cp, cm, x, y, shape, slot)
+
+    def add(self, tgt, ref, gt, rec):
+        key = (tuple(tgt.shape), tuple(gt.shape), rec.slot)
+        if self.waiting and (self.waiting[0][0] != key or len(self.waiting) == self.chunk):
+            self.flush()
+        self.waiting.append((key, tgt, ref, gt, rec))
+
+    def flush(self):
+        """One chunk: paste, ONE forward of the clean and the pasted pairs, metrics."""
+        from .flownets.utils_model import predict_flow
+        if not self.waiting:
+            return
+        items, self.waiting = self.waiting, []
+        K = len(items)
+        f32 = lambda ts: torch.cat([t.detach().to(torch.float32) for t in ts]).contiguous()
+        tgt, ref, gt = f32([it[1] for it in items]), f32([it[2] for it in items]), f32([it[3] for it in items])
+        recs = [it[4] for it in items]
+        dev = tgt.device
+        H, W, Hg, Wg, slot = int(tgt.shape[2]), int(tgt.shape[3]), int(gt.shape[2]), int(gt.shape[3]), recs[0].slot
+        stack = lambda name: torch.stack([getattr(r, name) for r in recs]).contiguous()
+        p_tgt, m_tgt = stack("patch_tgt"), stack("mask_tgt")
+        second = recs[0].patch_ref is not None
+        p_ref, m_ref = (stack("patch_ref"), stack("mask_ref")) if second else (None, None)
+        flow = stack("flow").to(torch.float32) if recs[0].flow is not None else None     # the script's torch.FloatTensor(flow_full)
+        places_host = np.ascontiguousarray(np.asarray([r.place() for r in recs], dtype=np.int32).reshape(K, 8))
+        places = torch.from_numpy(places_host).to(dev)
+        opt = lambda t: L.ptr(t) if t is not None else None
+        adv_tgt, adv_ref = torch.empty_like(tgt), torch.empty_like(ref)
+        lib = L.lib()
+        self._mark("start")
+        L.check(lib.ufr_eval_paste(L.ptr(tgt), L.ptr(ref), L.ptr(p_tgt), L.ptr(m_tgt), opt(p_ref), opt(m_ref), L.ptr(places),
+                                   places_host.ctypes.data, L.ptr(adv_tgt), L.ptr(adv_ref), K, H, W, slot, slot, self.lo, self.hi,
+                                   L.stream()), "eval paste")
+        self._mark("paste")
+        flows = predict_flow(self.net, None, torch.cat((tgt, adv_tgt)), torch.cat((ref, adv_ref)), self.args)
+        if tuple(flows.shape) != (2 * K, 2, H, W):
+            raise RuntimeError(f"the network returned a flow of shape {tuple(flows.shape)} for {2 * K} pairs of {H}x{W} frames")
+        flows = flows.contiguous()
+        if self.ws is None or self.ws.device != dev:
+            self.ws = torch.zeros(lib.ufr_eval_metrics_workspace_doubles(self.chunk), dtype=torch.float64, device=dev)
+        out = torch.zeros(K, 4, dtype=torch.float32, device=dev)
+        self._mark("forward")
+        L.check(lib.ufr_eval_metrics(L.ptr(flows[:K]), L.ptr(flows[K:]), L.ptr(gt), L.ptr(m_tgt), opt(m_ref), opt(flow), L.ptr(places),
+                                     places_host.ctypes.data, K, H, W, Hg, Wg, slot, slot, self.ignore, L.ptr(self.ws),
+                                     self.ws.numel(), L.ptr(out), 0, K, L.stream()), "eval metrics")
+        self._mark("metrics")
+        self.results.append(out)
+
+    def write_back(self):
+        """utils_patch.square_transform turns the CALLER's patch and mask in place; the accumulated turns are handed back."""
+        if not (self.square and not self.different and self.patch_d is not None):
+            return
+        for dst, src in ((self.patch, self.patch_d), (self.mask, self.mask_d)):
+            if torch.is_tensor(dst):
+                dst.copy_(src.to(dst.dtype))
+            else:
+                np.copyto(dst, src.cpu().numpy().astype(dst.dtype, copy=False))
+
+
+def evaluate_patch(flow_net, val_loader, patch, mask, patch_shape, args: Namespace, chunk=4) -> EvalResult:
+    """test_patch.py:242-466 without its images, CSV files and TensorBoard.
+
+    val_loader yields the reference's batch-1 items `(ref_past, tgt, ref, flow_gt[, disp_gt, calib, poses])` as HIP tensors
+    (frames [1,3,H,W], flow_gt [1,3,Hg,Wg] = (u, v, valid)); patch / mask: [1,3,S,S] numpy arrays or tensors, as
+    `utils_patch.get_patch_and_mask` returns them.  `args` fields (the script's defaults when absent): flownet, patch_type
+    ("circle"), norotate (False), different_pos (False), fixed_loc_x / fixed_loc_y (-1), HOMOGENUOUS (False), ignore_mask_flow
+    (False), true_motion (False).  The caller seeds `np.random` (the script: 1337); the draws are the script's, item by item,
+    whatever `chunk` is.  `true_motion`, and an item with calibration while neither different_pos nor HOMOGENUOUS is set, need the
+    3-D projection of the patch: NotImplementedError.  With `patch_type == "square"` the quarter turns accumulate in the caller's
+    patch and mask, like the reference's in-place `square_transform`.  The parameters are frozen like the attack steps freeze
+    them (`patch_attack.release(flow_net)` gives the flags back); the host synchronises once."""
+    from .patch_attack import ERROR_NAMES
+    if getattr(args, "true_motion", False):
+        _refuse_3d("true_motion")
+    if int(chunk) < 1:
+        raise ValueError("chunk must be positive")
+    if len(patch.shape) != 4 or tuple(patch.shape[:2]) != (1, 3) or tuple(mask.shape) != tuple(patch.shape):
+        raise ValueError("patch and mask must be [1,3,S,S], in patch coordinates")
+    ev = _Evaluation(flow_net, patch, mask, patch_shape, args, chunk)
+    ev.events = getattr(evaluate_patch, "_debug_events", None)
+    frozen = False
+    with torch.no_grad():
+        for item in val_loader:
+            tgt, ref, gt = item[1], item[2], item[3]
+            calibrated = len(item) > 5 and len(item[5]) > 0
+            if calibrated and not (ev.different or ev.homogeneous):
+                _refuse_3d("an item with calibration (neither different_pos nor HOMOGENUOUS is set)")
+            if tgt.dim() != 4 or tgt.shape[0] != 1 or tgt.shape[1] != 3 or ref.shape != tgt.shape:
+                raise ValueError("the loader yields batch-1 items: tgt and ref [1,3,H,W]")
+            if gt.dim() != 4 or gt.shape[0] != 1 or gt.shape[1] != 3:
+                raise ValueError("flow_gt must be [1,3,Hg,Wg] (u, v, valid)")
+            margin = int(item[4].max()) if calibrated else 0                          # test_patch.py:272-274
+            L.require_hip(tgt, "tgt_img", contiguous=False)
+            L.require_hip(ref, "ref_img", contiguous=False)
+            L.require_hip(gt, "flow_gt", contiguous=False)
+            dev = tgt.device
+            rec = ev.place(tuple(tgt.shape), margin, dev)
+            if not frozen:
+                L.freeze_parameters(flow_net)
+                flow_net.eval()
+                frozen = True
+            if ev.homogeneous:                                                        # test_patch.py:255-259
+                tgt, ref, gt = torch.full_like(tgt, 0.5), torch.full_like(ref, 0.5), torch.zeros_like(gt)
+            with torch.cuda.device(dev):
+                ev.add(tgt, ref, gt, rec)
+        if ev.waiting:
+            with torch.cuda.device(ev.waiting[0][1].device):
+                ev.flush()
+        ev.write_back()
+        if ev.results:
+            per_item = torch.cat(ev.results).cpu().numpy().astype(np.float64)        # the one host synchronisation of the call
+        else:
+            per_item = np.zeros((0, 4))
+    mean = per_item.mean(axis=0) if len(per_item) else np.zeros(4)
+    return EvalResult(per_item, mean, ev.locations, list(ERROR_NAMES))

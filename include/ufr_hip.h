@@ -1093,6 +1093,44 @@ int ufr_eval_metrics(const float* pred_clean, const float* pred_adv, const float
                      const float* flow, const int* places, const int* places_host, int K, int H, int W, int Hg, int Wg, int sh,
                      int sw, int ignore_mask_flow, double* ws, long ws_elems, float* out, int row0, int rows, ufr_stream_t stream);
 
+/* ---- global-attack evaluation over a validation set (csrc/global_eval.hip) ------------------------------------------------------
+ * global_attacks/perturb_main.py:466-812 runs, per validation item, a clean forward, the attack (or a fixed perturbation) and an
+ * attacked forward; global_attacks/log_utils.py:226-528 (`validate`) makes the table from the noises, both predictions and the
+ * ground truth.  K items of a chunk are served by two entries.
+ *
+ * ufr_global_apply: image0 / image1 [K,3,H,W], noise0 / noise1 [Kn,3,H,W], Kn = K or Kn = 1 (one perturbation for every item: the
+ *   universal case) -> adv0 = clamp(image0 + noise0, lo, hi), adv1 likewise: one float32 add and one clamp per element, bit-equal
+ *   to torch.clamp(image + noise, lo, hi).  One launch; 16-byte accesses when 3 * H * W % 4 == 0 and all six pointers are 16-byte
+ *   aligned, a scalar path otherwise.
+ * ufr_global_metrics: pred_clean / pred_adv [K,2,H,W]; gt [Kg,C,Hg,Wg], C = 3 (u, v, valid) or C = 2, Kg = K or Kg = 1 (one ground
+ *   truth for every item: an arbitrary target); noise0 / noise1 [Kn,3,H,W], Kn = K or 1, both given or both NULL (Kn is then not
+ *   read) -> out[row0 + k] = ten FLOAT64 values of a result buffer of `rows` rows:
+ *       (noise0_L0, noise0_L1, noise1_L0, noise1_L1, epe_clean, epe_adv, l1_clean, l1_adv, cossim_clean, cossim_adv)
+ *   the noise columns NaN when the noise is NULL.  One pass over the ground-truth pixels and one over the noise, in float64:
+ *     p   = the prediction resized bilinearly, align_corners = False (the rule of ufr_sweep_metrics: the identity when the sizes
+ *           agree), then (p_u * Wg/W, p_v * Hg/H)                                           (global_attacks/perturb_model.py:43-45)
+ *     w   = valid (C = 3) or 1 (C = 2);   den = sum(valid) + 1e-8 (C = 3) or Hg * Wg (C = 2)
+ *     epe = sum(w * |(g_u - p_u, g_v - p_v)|) / den                                                                      (:38-59)
+ *     cos = sum(w * sum_c (g_c / max(|g|, 1e-8)) * (p_c / max(|p|, 1e-8))) / den: ufr_sweep_metrics' cosine_similarity rule, here
+ *           of the RESCALED prediction, as :62-81 rescales it first
+ *     l1  = m * sum(valid) / (sum(valid) + 1e-8) (C = 3) or m (C = 2), m = the mean of |p - g| over all entries of both channels
+ *           and all pixels that are not NaN; `valid` does NOT weight m -- the reference's quirk                          (:84-99)
+ *     noise_L0 = max |noise| (eval_utils.lp_norm(p=0); a NaN stays, as in np.max), noise_L1 = sum |noise| / (H * W) (lp_norm(p=1,
+ *           axis=-1) on the [H,W,3] view: the mean over pixels of the channel sum)
+ *   A NaN in the ground truth therefore leaves l1 (which skips it) and turns epe and cos into NaN, as in the reference.  Workgroup
+ *   partials (eleven sums and a maximum per noise) in `ws` (ufr_global_metrics_workspace_doubles(K) doubles) are combined in a fixed
+ *   order by a second launch; the workgroup count is a function of the sizes (and of whether a noise is given) alone, never of the
+ *   alignment that picks the 16-byte walk over the noise: no float atomics, two runs are bit-identical.
+ *   No resized prediction is written to memory.
+ * Refused (UFR_EINVAL + ufr_last_error) before any launch: null pointers, one noise without the other, K < 1, non-positive sizes,
+ *   Kn / Kg outside {1, K}, C outside {2, 3}, lo > hi, rows outside the result buffer, a workspace that is too small. */
+int ufr_global_apply(const float* image0, const float* image1, const float* noise0, const float* noise1, float* adv0, float* adv1,
+                     int K, int Kn, int H, int W, float lo, float hi, ufr_stream_t stream);
+long ufr_global_metrics_workspace_doubles(int K);   /* -1 when K < 1 */
+int ufr_global_metrics(const float* pred_clean, const float* pred_adv, const float* gt, const float* noise0, const float* noise1, int K,
+                       int Kg, int Kn, int C, int H, int W, int Hg, int Wg, double* ws, long ws_elems, double* out, int row0, int rows,
+                       ufr_stream_t stream);
+
 /* ---- feature-map statistics (csrc/feature_stats.hip) -------------------------------------------------------------------------
  * patch_attacks/test_patch_embeddings.py takes np.mean over the pixels of every feature map of a forward; here the maps stay where
  * the engine left them and only their per-image, per-channel SUMS leave the device, all segments of a forward in one result matrix.

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 from argparse import Namespace
 
+import numpy as np
 import torch
 from ._lib import engine_cache as _engine_cache
 
@@ -273,3 +274,66 @@ def attack(model, img0_var, img1_var, universal_perturbation_var, target_var, ar
     step.load(img0_var, img1_var, universal_perturbation_var, target_var)
     step.run(args.n_step)
     return step.adv0.detach().clone(), None, step.adv1.detach().clone(), step.delta.detach().clone()
+
+
+def validation(universal_perturbation, val_loader, model, epoch, args: Namespace, chunk=4):
+    """Drop-in for global_attacks/universal_perturbation.py::validation (:533-566, :664) without its writer and logger: the
+    per-epoch check of a universal perturbation [1,2,3,H,W].  Per chunk of up to `chunk` consecutive 7-tuple items
+    `(ref_past, tgt, ref_future, flow_gt, _, _, _)` of equal sizes: `add_universal_perturbation` as ONE ufr_global_apply (its
+    asymmetric indexing kept: frame 0 takes `[0, 0]`, frame 1 `[:, 1]`), ONE forward of the 2K clean and perturbed pairs, ONE
+    ufr_global_metrics (global_eval.py); the host reads once.  Returns `(errors_avg, ["epe", "adv_epe", "cos_sim", "adv_cos_sim"])`.
+    `epoch` only labelled the reference's images."""
+    from .global_eval import NAMES, Chunks
+    error_names = ["epe", "adv_epe", "cos_sim", "adv_cos_sim"]
+    if universal_perturbation.dim() != 5 or universal_perturbation.shape[1] != 2:
+        raise Exception("Universarial perturbation: first dimension must be 2!")
+    if universal_perturbation.shape[0] != 1:
+        raise ValueError("validation takes ONE universal perturbation [1,2,3,H,W]: with more, `[:, 1]` gives the second frame another "
+                         "batch size than the first")
+    L.freeze_parameters(model)
+    model.eval()
+    ev = Chunks(model, args, chunk, with_noise=False)
+    noise = None
+    for data in val_loader:
+        _, tgt_img, ref_img_future, flow_gt = data[0], data[1], data[2], data[3]
+        L.require_hip(tgt_img, "tgt_img", contiguous=False)
+        if noise is None or noise[0].device != tgt_img.device:
+            up = universal_perturbation.detach().to(tgt_img.device, torch.float32)
+            noise = (up[0, 0][None].contiguous(), up[:, 1].contiguous())
+        if tuple(noise[0].shape) != tuple(tgt_img.shape):
+            raise ValueError(f"the universal perturbation is {tuple(noise[0].shape)}, the item is {tuple(tgt_img.shape)}")
+        with torch.cuda.device(tgt_img.device):
+            ev.add(tgt_img, ref_img_future, flow_gt, noise, None)
+    if ev.waiting:
+        with torch.cuda.device(ev.waiting[0][1].device):
+            ev.flush()
+    per_item, _ = ev.read()
+    cols = [NAMES.index(n) for n in ("epe_clean", "epe_adv", "cossim_clean", "cossim_adv")]
+    avg = per_item[:, cols].mean(axis=0) if len(per_item) else np.zeros(4)
+    return [float(v) for v in avg], error_names
+
+
+def train(universal_perturbation, train_loader, model, args: Namespace):
+    """Drop-in for global_attacks/universal_perturbation.py::train (:354-397) without its writer and logger: the sequential loop
+    over `attack` that carries the perturbation from sample to sample.  Items are `(tgt, [ref_past, ref_future])` or
+    `(tgt, ref, _, _)`; the target is minus the clean prediction, or with `add_gaussian` the clean prediction plus one host
+    `torch.randn` draw of its shape.  Returns the carried perturbation [B,2,3,H,W]."""
+    model.eval()
+    for data in train_loader:
+        if len(data) == 2:
+            tgt_img, ref_img = data
+        elif len(data) == 4:
+            tgt_img, ref_img, _, _ = data
+            ref_img = [ref_img, ref_img]
+        else:
+            raise NotImplementedError
+        tgt_img, ref_past, ref_future = tgt_img.cuda(), ref_img[0].cuda(), ref_img[1].cuda()
+        flow_pred = predict_flow(model, ref_past, tgt_img, ref_future, args)
+        universal_perturbation = universal_perturbation.cuda()
+        if not getattr(args, "add_gaussian", False):
+            target = -1 * flow_pred.detach().clone()
+        else:
+            target = flow_pred.detach().clone()
+            target = target + 1 * torch.randn(target.shape).cuda()
+        _, _, _, universal_perturbation = attack(model, tgt_img, ref_future, universal_perturbation, target_var=target, args=args)
+    return universal_perturbation

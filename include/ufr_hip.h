@@ -1131,6 +1131,45 @@ int ufr_global_metrics(const float* pred_clean, const float* pred_adv, const flo
                        int Kg, int Kn, int C, int H, int W, int Hg, int Wg, double* ws, long ws_elems, double* out, int row0, int rows,
                        ufr_stream_t stream);
 
+/* ---- validation of the fine-tuning loop (csrc/validation.hip) -------------------------------------------------------------------
+ * training/evaluate.py:270-392 (`validate_chairs`, `validate_sintel`, `validate_kitti`) pads every item with `InputPadder`
+ * (models/raft/utils/utils.py:7-30), runs one batch-1 forward, copies the prediction to the host and keeps a per-pixel error array
+ * per item.  K items of a chunk are served by two entries.
+ *
+ * ufr_validation_pad: image1 / image2 [K,3,H,W] -> out1 / out2 [K,3,H + top + bottom,W + left + right], the border replicated:
+ *   out[k,c,y,x] = image[k,c,clamp(y - top, 0, H - 1),clamp(x - left, 0, W - 1)], bit-equal to
+ *   F.pad(image, [left, right, top, bottom], mode="replicate").  With divide_by_255 != 0 every value is, in the same pass,
+ *   MULTIPLIED by the float32 reciprocal fl(1 / 255) (0x1.010102p-8), one rounding: that is what torch's device kernel computes for
+ *   `F.pad(...) / 255.0` -- a divisor that is a host scalar becomes its reciprocal; the host kernel divides, and differs in the last
+ *   bit for most values.  One launch covers both frames.  16-byte stores when the padded row length is a multiple of 4 and both
+ *   outputs are 16-byte aligned, then 16-byte loads too for the interior when W % 4 == 0, left % 4 == 0 and both inputs are
+ *   aligned; one float per access otherwise.
+ * ufr_validation_metrics: pred [K,2,Hp,Wp] (the prediction on the PADDED frame; pixel (y, x) of the item is read at
+ *   (y + top, x + left), the unpadded prediction is never written to memory), gt [K,2,H,W], valid [K,H,W] or NULL (every pixel
+ *   counts as valid) -> out[row0 + k] = UFR_VALIDATION_COLS FLOAT64 values of a result buffer of `rows` rows:
+ *       (sum of e, entries, entries with e < 1, with e < 3, with e < 5, sum of e over valid pixels, valid entries,
+ *        valid entries with e > 3 and e / |gt| > 0.05)
+ *   where a pixel is valid when valid >= 0.5 and its entries e are, by mode,
+ *       0  one per pixel:  sqrt((p_u - g_u)^2 + (p_v - g_v)^2)                       validate_chairs (:290), validate_kitti (:374)
+ *       1  two per pixel:  sqrt((p_u - g_u)^2), sqrt((p_v - g_v)^2)                  validate_sintel (:328 sums over the batch axis)
+ *       2  two per pixel:  sqrt((p_u - g_u)^2), sqrt((p_u - g_v)^2)                  validate_sintel with flowNetC (:322, :326)
+ *   e, |gt| = sqrt(g_u^2 + g_v^2) and e / |gt| are float32 with every operation rounded on its own (no contraction, correctly
+ *   rounded sqrt and division): each value that meets a threshold is the IEEE result of torch's float32 expression.  (torch's own
+ *   sqrt is within one unit in the last place of it -- the host kernel goes through a vector maths library for large tensors, the
+ *   device kernel through the native instruction -- so no kernel can be bit-equal to both.)  |gt| = 0 follows IEEE (e / 0 = inf).
+ *   A NaN compares false and poisons the sums it enters, as in numpy.  The sums are float64, the counts exact integers.  Workgroup
+ *   partials in `ws` (ufr_validation_metrics_workspace_doubles(K, H, W) doubles) are added in a fixed order by a second launch; the
+ *   workgroup count min(128, ceil(H * W / 256)) per item follows from the sizes alone: no float atomics, two runs are bit-identical.
+ * Refused (UFR_EINVAL + ufr_last_error) before any launch: null pointers (valid may be NULL), K < 1, non-positive sizes, negative
+ *   pads, a crop that leaves the padded frame (top + H > Hp or left + W > Wp), a mode outside 0..2, rows outside the result buffer,
+ *   a workspace that is too small. */
+#define UFR_VALIDATION_COLS 8
+int ufr_validation_pad(const float* image1, const float* image2, float* out1, float* out2, int K, int H, int W, int top, int bottom,
+                       int left, int right, int divide_by_255, ufr_stream_t stream);
+long ufr_validation_metrics_workspace_doubles(int K, int H, int W);   /* -1 when K, H or W < 1 */
+int ufr_validation_metrics(const float* pred, const float* gt, const float* valid, int K, int Hp, int Wp, int top, int left, int H,
+                           int W, int mode, double* ws, long ws_elems, double* out, int row0, int rows, ufr_stream_t stream);
+
 /* ---- feature-map statistics (csrc/feature_stats.hip) -------------------------------------------------------------------------
  * patch_attacks/test_patch_embeddings.py takes np.mean over the pixels of every feature map of a forward; here the maps stay where
  * the engine left them and only their per-image, per-channel SUMS leave the device, all segments of a forward in one result matrix.

@@ -298,6 +298,8 @@ SIGNATURES = {
     "ufr_eval_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
     "ufr_global_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp],
     "ufr_global_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
+    "ufr_validation_pad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ufr_validation_metrics": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
     "ufr_feature_stats": [C.POINTER(FeatureStatsSeg), _i, _vp, _l, _vp, _i, _l, _l, _vp],
     "ufr_abs_sums": [_vp, _vp, _l, _vp, _l, _vp, _vp],
     "ufr_momentum_update": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _vp],
@@ -320,6 +322,7 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i]),
          "ufr_eval_metrics_workspace_doubles": (C.c_long, [_i]),
          "ufr_global_metrics_workspace_doubles": (C.c_long, [_i]),
+         "ufr_validation_metrics_workspace_doubles": (C.c_long, [_i, _i, _i]),
          "ufr_feature_stats_workspace_doubles": (C.c_long, [C.POINTER(FeatureStatsSeg), _i]),
          "ufr_abs_sums_workspace_doubles": (C.c_long, [_l]),
          "ufr_diverse_workspace_doubles": (C.c_long, [_i, _i, _i, _i])}

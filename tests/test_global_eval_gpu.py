@@ -68,7 +68,7 @@ def test_apply_is_bit_equal_to_torch(h, w, kn, shifted):
 MK, MH, MW = 3, 24, 40
 # ground-truth sizes: smaller, equal (the resize is the identity; 960 pixels are several workgroups of one item), larger, and 9 x 13,
 # which fills less than one workgroup
-MSIZES = [(23, 37), (24, 40), (31, 53), (9, 13)]
+MSIZES = [(23, 37), (24, 40), (31, 53), (9, 13), (130, 254)]          # the last: 129 > 128 workgroups, a second pixel per thread
 
 
 def _metric_operands(hg, wg, C, nan_pixels=False):

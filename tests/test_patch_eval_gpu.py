@@ -234,7 +234,7 @@ def _run_eval_metrics(pred_c, pred_a, gt, m_tgt, m_ref, flow, ignore):
     return out[1:-1].clone()
 
 
-@pytest.mark.parametrize("hg,wg", [(60, 100), (64, 96)])
+@pytest.mark.parametrize("hg,wg", [(60, 100), (64, 96), (130, 254)])          # the last: 129 > 128 workgroups, a second pixel per thread
 @pytest.mark.parametrize("second,with_flow,ignore", [(True, True, 0), (True, True, 1), (True, False, 0), (False, False, 0),
                                                      (False, False, 1), (False, True, 0)])
 def test_metrics_against_float64_restatement(hg, wg, second, with_flow, ignore):

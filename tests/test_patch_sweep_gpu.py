@@ -188,7 +188,8 @@ def _run_metrics(pred, gt, mask_p, rows, valid_in_patch):
 
 
 @pytest.mark.parametrize("hg,wg,valid_in_patch,with_mask", [(60, 100, 1, True), (60, 100, 0, True), (64, 96, 1, True),
-                                                           (60, 100, 1, False)])
+                                                           (60, 100, 1, False),
+                                                           (130, 254, 1, True)])       # 129 > 128 workgroups: a second pixel per thread
 def test_metrics_against_float64_restatement(hg, wg, valid_in_patch, with_mask):
     """Bound per value: the larger of 1e-6 * |value| (what tests/test_flow_oracle_cpu.py holds these metrics to) and 4 x the error
     of the float32 torch spelling against the same float64 values (the kernel's per-pixel rounding sequence may differ from

@@ -192,7 +192,7 @@ def _metric_operands(h, w, with_valid):
 
 @pytest.mark.parametrize("with_valid", [False, True], ids=["no-mask", "mask"])
 @pytest.mark.parametrize("mode", [0, 1, 2])
-@pytest.mark.parametrize("h,w", [(5, 7), (21, 35), (125, 187)])            # one workgroup, three, 92 per item
+@pytest.mark.parametrize("h,w", [(5, 7), (21, 35), (125, 187), (129, 257)])  # workgroups: 1, 3, 92, 130 > 128 (a second pixel per thread)
 def test_metrics_against_the_restatement(h, w, mode, with_valid):
     pred, top, left, gt, valid = _metric_operands(h, w, with_valid)
     want = _restated(pred, top, left, gt, valid, mode)

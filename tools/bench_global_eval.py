@@ -65,6 +65,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_global_eval: no HIP device; nothing is measured without one")
     from understanding_flow_robustness_amd import global_eval as ge
+    from understanding_flow_robustness_amd.chunked_eval import recorded_events, stage_ms
     from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
     from understanding_flow_robustness_amd.perturb_model import PerturbationsModel
     H, W, n = opt.height, opt.width, opt.items
@@ -129,16 +130,7 @@ def main():
         # stacking of what the attacks returned; the attacks themselves run between the chunks and are not inside these events)
         split = {}
         for c in chunks:
-            ge.evaluate_perturbation._debug_events = events = []
-            try:
-                native(c)
-            finally:
-                ge.evaluate_perturbation._debug_events = None
-            torch.cuda.synchronize()
-            acc = {"apply": 0.0, "forward": 0.0, "metrics": 0.0}
-            for (_, e0), (stage, e1) in zip(events, events[1:]):
-                if stage != "start":
-                    acc[stage] += e0.elapsed_time(e1)
+            acc = stage_ms(recorded_events(ge.evaluate_perturbation, lambda: native(c)), ("apply", "forward", "metrics"))
             total = sum(acc.values())
             split[f"chunk{c}"] = {"ms_per_item": {k: v / n for k, v in acc.items()},
                                   "share": {k: (v / total if total > 0 else 0.0) for k, v in acc.items()}}

@@ -70,6 +70,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_patch_eval: no HIP device; nothing is measured without one")
     from understanding_flow_robustness_amd import patch_eval as pe
+    from understanding_flow_robustness_amd.chunked_eval import recorded_events, stage_ms
     from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
     from understanding_flow_robustness_amd.utils_patch import createCircularMask
     H, W, S, n = opt.height, opt.width, opt.patch, opt.items
@@ -122,16 +123,7 @@ def main():
     # the two entries' device time, from device events, in a run of its own per chunk size
     split = {}
     for c in chunks:
-        pe.evaluate_patch._debug_events = events = []
-        try:
-            native(c)
-        finally:
-            pe.evaluate_patch._debug_events = None
-        torch.cuda.synchronize()
-        acc = {"paste": 0.0, "forward": 0.0, "metrics": 0.0}
-        for (_, e0), (stage, e1) in zip(events, events[1:]):
-            if stage != "start":
-                acc[stage] += e0.elapsed_time(e1)
+        acc = stage_ms(recorded_events(pe.evaluate_patch, lambda: native(c)), ("paste", "forward", "metrics"))
         split[f"chunk{c}"] = {k: v / n for k, v in acc.items()}
     result = {
         "what": "patch evaluation over a validation set, --different_pos", "network": "FlowNetC (synthetic weights, seed 0)",

@@ -70,6 +70,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_patch_sweep: no HIP device; nothing is measured without one")
     from understanding_flow_robustness_amd import patch_sweep as ps
+    from understanding_flow_robustness_amd.chunked_eval import recorded_events, stage_ms
     from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
     from understanding_flow_robustness_amd.utils_patch import createCircularMask
     H, W, S, stride, chunk = opt.height, opt.width, opt.patch, opt.stride, opt.chunk
@@ -114,16 +115,7 @@ def main():
             times[name].append(time.perf_counter() - t0)
         print(f"window {w}: " + ", ".join(f"{k} {v[-1]:.3f} s" for k, v in times.items()), flush=True)
     # the windowed path's stages, from device events, in a run of its own
-    ps.sweep_patch_locations._debug_events = events = []
-    try:
-        forms["windowed"]()
-    finally:
-        ps.sweep_patch_locations._debug_events = None
-    torch.cuda.synchronize()
-    split = {s: 0.0 for s in ps.WINDOWED_STAGES}
-    for (_, e0), (stage, e1) in zip(events, events[1:]):
-        if stage != "start":
-            split[stage] += e0.elapsed_time(e1)
+    split = stage_ms(recorded_events(ps.sweep_patch_locations, forms["windowed"]), ps.WINDOWED_STAGES)
     result = {
         "what": "patch location sweep, one frame pair", "network": "FlowNetC (synthetic weights, seed 0)", "frame": [H, W],
         "ground_truth": [hg, wg], "patch": S, "stride": stride, "positions": n, "chunk": chunk, "windows": opt.windows,

@@ -46,6 +46,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_validation: no HIP device; nothing is measured without one")
     from understanding_flow_robustness_amd import validation as V
+    from understanding_flow_robustness_amd.chunked_eval import recorded_events, stage_ms
     from understanding_flow_robustness_amd.flownets.utils_model import fetch_model
     n, chunks = opt.items, (1, 4, 8)
     configs = {}
@@ -93,16 +94,7 @@ def main():
             print(f"{name}: window {w}: " + ", ".join(f"{k} {v[-1]:.3f} s" for k, v in times.items()), flush=True)
         split = {}
         for c in chunks:
-            V._fused_table._debug_events = events = []
-            try:
-                evaluate(True, c)
-            finally:
-                V._fused_table._debug_events = None
-            torch.cuda.synchronize()
-            acc = {"pad": 0.0, "forward": 0.0, "metrics": 0.0}
-            for (_, e0), (stage, e1) in zip(events, events[1:]):
-                if stage != "start":
-                    acc[stage] += e0.elapsed_time(e1)
+            acc = stage_ms(recorded_events(V._fused_table, lambda: evaluate(True, c)), ("pad", "forward", "metrics"))
             total = sum(acc.values())
             split[f"chunk{c}"] = {"ms_per_item": {k: v / n for k, v in acc.items()},
                                   "share": {k: (v / total if total > 0 else 0.0) for k, v in acc.items()}}

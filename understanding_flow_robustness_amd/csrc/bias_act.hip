@@ -48,7 +48,7 @@ __global__ void leaky_bwd(const float* __restrict__ y, const float* __restrict__
     gx[i] = y[i] > 0.f ? gy[i] : gy[i] * slope;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using ufr::aligned16;
 
 }  // namespace
 
@@ -70,7 +70,7 @@ extern "C" int ufr_leaky_backward(const float* y, const float* grad_y, float* gr
                                   ufr_stream_t stream) {
   UFR_REQUIRE(y && grad_y && grad_x && total > 0 && slope >= 0.f, "leaky backward: bad argument");
   hipStream_t st = ufr::as_stream(stream);
-  if ((total & 3) == 0 && aligned16(y) && aligned16(grad_y) && aligned16(grad_x))
+  if ((total & 3) == 0 && aligned16(y, grad_y, grad_x))
     leaky_bwd_vec4<<<ufr::stream_grid(total / 4, 256), 256, 0, st>>>(reinterpret_cast<const float4*>(y),
                                                                       reinterpret_cast<const float4*>(grad_y),
                                                                       reinterpret_cast<float4*>(grad_x), total / 4, slope);

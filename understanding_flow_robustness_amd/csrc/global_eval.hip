@@ -6,27 +6,26 @@
 //                       serve all of them (a universal perturbation);
 //   ufr_global_metrics  the six flow metrics of `validate` (end-point error, L1 and cosine similarity of the clean and of the
 //                       attacked prediction, each resized to the ground truth) and the four noise norms, one pass over the
-//                       ground-truth pixels and one over the noise; float64 throughout, workgroup partials + a finalize launch (the
-//                       pattern of patch_eval.hip and feature_stats.hip): no float atomics, two runs are bit-identical.
+//                       ground-truth pixels and one over the noise; float64 throughout, the per-item metrics scheme of ufr_common.h.
 // The reference does, per item: five D2H copies, five `FloatTensor` uploads inside `validate`, six metric calls that each resize
 // the prediction and end in `.item()`, and four numpy norms.
-#include <cstdint>
-
 #include "ufr_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSlots = 128;            // workgroups (= partials) per item at most
+constexpr int kSlots = ufr::kMetricSlots;
 // partials of one workgroup: [0..3] clean: w * epe, w * cos, sum |d| over non-NaN entries, their count; [4..7] attacked: the same;
 // [8] sum of w; [9] sum |noise0|; [10] sum |noise1|; [11] max |noise0|; [12] max |noise1|
 constexpr int kPart = 13;
 constexpr int kSums = 11;
 constexpr int kOut = 10;
 
-using ufr::dev::bilinear;
-using ufr::dev::bilinear_source;
-using ufr::dev::block_sum;
+using ufr::aligned16;
+using ufr::dev::epe_cos;
+using ufr::dev::FlowTaps;
+using ufr::dev::flow_taps;
+using ufr::dev::sample;
 
 // numpy's max: a NaN stays
 __device__ __forceinline__ double nan_max(double m, double a) { return (a > m || a != a) ? a : m; }
@@ -65,12 +64,12 @@ __global__ __launch_bounds__(kBlock) void global_apply_kernel(const float* __res
   }
 }
 
-// perturb_model.py:38-99 for one pixel and one prediction: sum = (w * epe, w * cos, sum |d| over the non-NaN entries, their count)
+// perturb_model.py:38-99 for one pixel and one prediction (fu, fv), ALREADY rescaled: the error against it and the cosine with it;
+// sum = (w * epe, w * cos, sum |d| over the non-NaN entries, their count)
 __device__ __forceinline__ void pixel_metrics(double gu, double gv, double w, double fu, double fv, double* sum) {
   const double du = fu - gu, dv = fv - gv;
-  const double epe = sqrt(du * du + dv * dv);
-  const double ng = fmax(sqrt(gu * gu + gv * gv), 1e-8), nf = fmax(sqrt(fu * fu + fv * fv), 1e-8);
-  const double cs = (gu / ng) * (fu / nf) + (gv / ng) * (fv / nf);
+  double epe, cs;
+  epe_cos(du, dv, gu, gv, fu, fv, epe, cs);
   sum[0] += epe * w;
   sum[1] += cs * w;
   const double au = fabs(du), av = fabs(dv);
@@ -97,16 +96,9 @@ __global__ __launch_bounds__(kBlock) void global_metrics_kernel(const float* __r
   double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double mx0 = 0.0, mx1 = 0.0;
   for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
-    const int yg = (int)(p / Wg), xg = (int)(p - (long)yg * Wg);
-    int y0, y1, x0, x1;
-    double ly, lx;
-    bilinear_source(yg, sy, H, y0, y1, ly);
-    bilinear_source(xg, sx, W, x0, x1, lx);
-    const long r0 = (long)y0 * W, r1 = (long)y1 * W;
-    const double pu = bilinear((double)cu[r0 + x0], (double)cu[r0 + x1], (double)cu[r1 + x0], (double)cu[r1 + x1], ly, lx) * scale_u;
-    const double pv = bilinear((double)cv[r0 + x0], (double)cv[r0 + x1], (double)cv[r1 + x0], (double)cv[r1 + x1], ly, lx) * scale_v;
-    const double qu = bilinear((double)au[r0 + x0], (double)au[r0 + x1], (double)au[r1 + x0], (double)au[r1 + x1], ly, lx) * scale_u;
-    const double qv = bilinear((double)av[r0 + x0], (double)av[r0 + x1], (double)av[r1 + x0], (double)av[r1 + x1], ly, lx) * scale_v;
+    const FlowTaps s = flow_taps(p, Wg, sy, sx, H, W);
+    const double pu = sample(cu, s) * scale_u, pv = sample(cv, s) * scale_v;
+    const double qu = sample(au, s) * scale_u, qv = sample(av, s) * scale_v;
     const double gu = (double)gk[p], gv = (double)gk[HWg + p];
     const double w = C == 3 ? (double)gk[2 * HWg + p] : 1.0;
     pixel_metrics(gu, gv, w, pu, pv, sum);
@@ -140,11 +132,7 @@ __global__ __launch_bounds__(kBlock) void global_metrics_kernel(const float* __r
       }
     }
   }
-  double* __restrict__ mine = part + ((long)k * kSlots + blockIdx.x) * kPart;
-  for (int q = 0; q < kSums; ++q) {
-    const double t = block_sum<kBlock>(sum[q], lds);
-    if (threadIdx.x == 0) mine[q] = t;
-  }
+  double* __restrict__ mine = ufr::dev::store_partial<kBlock, kSums, kPart>(sum, lds, part, k, kSlots);
   const double t0 = block_max<kBlock>(mx0, lds);
   const double t1 = block_max<kBlock>(mx1, lds);
   if (threadIdx.x == 0) { mine[11] = t0; mine[12] = t1; }
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(kBlock) void global_metrics_finalize_kernel(const d
   const bool mine = (int)threadIdx.x < slots;
   const double* __restrict__ p = part + ((long)k * kSlots + (mine ? threadIdx.x : 0)) * kPart;
   double t[kPart];
-  for (int q = 0; q < kSums; ++q) t[q] = block_sum<kBlock>(mine ? p[q] : 0.0, lds);
+  ufr::dev::item_totals<kBlock, kSums, kPart>(part, k, kSlots, slots, lds, t);
   for (int q = kSums; q < kPart; ++q) t[q] = block_max<kBlock>(mine ? p[q] : 0.0, lds);
   if (threadIdx.x == 0) {
     double* __restrict__ o = out + (long)k * kOut;
@@ -178,8 +166,6 @@ __global__ __launch_bounds__(kBlock) void global_metrics_finalize_kernel(const d
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int ufr_global_apply(const float* image0, const float* image1, const float* noise0, const float* noise1, float* adv0,
@@ -192,8 +178,7 @@ extern "C" int ufr_global_apply(const float* image0, const float* image1, const 
   hipStream_t st = ufr::as_stream(stream);
   const long CHW = 3L * H * W, total = (long)K * CHW;
   const int broadcast = Kn == 1 && K > 1 ? 1 : 0;
-  if (CHW % 4 == 0 && aligned16(image0) && aligned16(image1) && aligned16(noise0) && aligned16(noise1) && aligned16(adv0) &&
-      aligned16(adv1))
+  if (CHW % 4 == 0 && aligned16(image0, image1, noise0, noise1, adv0, adv1))
     global_apply_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(image0, image1, noise0, noise1, adv0, adv1,
                                                                                  total / 4, CHW, broadcast, lo, hi);
   else
@@ -215,17 +200,14 @@ extern "C" int ufr_global_metrics(const float* pred_clean, const float* pred_adv
   UFR_REQUIRE(noise0 == nullptr || Kn == 1 || Kn == K, "global metrics: %d noise items for %d items (1 or %d)", Kn, K, K);
   UFR_REQUIRE(C == 2 || C == 3, "global metrics: %d ground-truth channels (2 or 3)", C);
   UFR_REQUIRE((long)H * W < (1L << 29) && (long)Hg * Wg < (1L << 29), "global metrics: too many pixels");
-  UFR_REQUIRE(row0 >= 0 && rows > 0 && (long)row0 + K <= rows, "global metrics: rows %d .. %ld leave the result buffer of %d rows", row0,
-              (long)row0 + K - 1, rows);
-  UFR_REQUIRE(ws_elems >= ufr_global_metrics_workspace_doubles(K), "global metrics: workspace of %ld doubles, %ld needed", ws_elems,
-              ufr_global_metrics_workspace_doubles(K));
+  if (int rc = ufr::check_result_rows("global metrics", row0, K, rows)) return rc;
+  if (int rc = ufr::check_workspace("global metrics", ws_elems, ufr_global_metrics_workspace_doubles(K))) return rc;
   hipStream_t st = ufr::as_stream(stream);
   const long npix = (long)Hg * Wg, CHW = 3L * H * W;
-  const int vec = noise0 != nullptr && CHW % 4 == 0 && aligned16(noise0) && aligned16(noise1) ? 1 : 0;
+  const int vec = noise0 != nullptr && CHW % 4 == 0 && aligned16(noise0, noise1) ? 1 : 0;
   // the workgroup count fixes the order of the sums: it follows from the sizes alone, never from the alignment that picks `vec`
   const long quads = noise0 != nullptr ? (CHW + 3) / 4 : 0;
-  int slots = ufr::ceil_div(quads > npix ? quads : npix, kBlock);
-  if (slots > kSlots) slots = kSlots;
+  const int slots = ufr::metric_slots(quads > npix ? quads : npix, kBlock);
   global_metrics_kernel<<<dim3(slots, K), kBlock, 0, st>>>(pred_clean, pred_adv, gt, noise0, noise1, Kg == K ? 1 : 0, Kn == K ? 1 : 0, C,
                                                            H, W, Hg, Wg, vec, ws);
   if (int rc = ufr::launched("global_metrics_kernel")) return rc;

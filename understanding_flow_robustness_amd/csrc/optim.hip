@@ -49,18 +49,6 @@ __device__ inline long head_elems(const void* p, long n) {
   return h < n ? h : n;
 }
 
-// the sum over the workgroup in a fixed order (lane tree inside a wave, then the waves in ascending order); valid in thread 0
-__device__ inline double block_sum(double v, double* lds) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < kBlock / 64; ++i) t += lds[i];
-  return t;
-}
-
 __global__ __launch_bounds__(kBlock) void grad_sumsq_kernel(SegArgs a, double* __restrict__ partials) {
   __shared__ double lds[kBlock / 64];
   const int wg = blockIdx.x, s = find_seg(a, wg);
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void grad_sumsq_kernel(SegArgs a, double* _
     const long t = tail0 + threadIdx.x;
     if (t < n) acc += (double)g[t] * g[t];
   }
-  const double total = block_sum(acc, lds);
+  const double total = ufr::dev::block_sum<kBlock>(acc, lds);   // lane tree inside a wave, then the waves in ascending order
   if (threadIdx.x == 0) partials[wg] = total;
 }
 

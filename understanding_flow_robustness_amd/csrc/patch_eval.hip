@@ -5,26 +5,28 @@
 //   ufr_eval_paste    the K adversarial pairs, one launch;
 //   ufr_eval_metrics  resized predictions, resized canvas masks of both records, the occlusion of the ground truth by the second
 //                     record, the patch's own flow resized by scipy's zoom rule, the blend and all four metrics in one pass over the
-//                     ground-truth pixels; float64 throughout, workgroup partials + a finalize launch (the pattern of
-//                     patch_sweep.hip and train_loss.hip): no float atomics, two runs are bit-identical.
+//                     ground-truth pixels; float64 throughout, the per-item metrics scheme of ufr_common.h.
 // The reference does, per item: six canvas-sized host arrays and a canvas-sized flow, five H2D copies, ten torch operators for the
 // pastes, two bilinear resizes, a scipy.ndimage.zoom of the canvas flow on the host, ten operators for the blends and four metric
 // calls that each end in `.item()`.
-#include <cstdint>
-
 #include "ufr_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSlots = 128;            // workgroups (= partials) per item at most
+constexpr int kSlots = ufr::kMetricSlots;
 constexpr int kSums = 6;               // clean: valid * epe, valid * cos, valid; attacked: the same three
 constexpr int kPlace = 8;              // places[k] = {y_tgt, x_tgt, h_tgt, w_tgt, y_ref, x_ref, h_ref, w_ref}
 
-using ufr::dev::bilinear;
-using ufr::dev::bilinear_source;
-using ufr::dev::block_sum;
+using ufr::aligned16;
+using ufr::dev::Corners;
+using ufr::dev::corners;
+using ufr::dev::epe_cos;
+using ufr::dev::FlowTaps;
+using ufr::dev::flow_taps;
 using ufr::dev::paste_clamped;
+using ufr::dev::resized_canvas;
+using ufr::dev::sample;
 
 // idx runs over [K,3,H,W] in units of V floats; the first frame takes record 0 of its item, the second frame record `second`
 template <int V>
@@ -85,34 +87,10 @@ __global__ __launch_bounds__(kBlock) void eval_paste_kernel(const float* __restr
 }
 
 // ---- metrics ------------------------------------------------------------------------------------------------------------------
-// a record's canvas at frame rows y0 / y1 and columns x0 / x1 (already inside the frame): the slot inside the h x w rectangle at
-// (oy, ox), 0 outside
-struct Corners {
-  int i0, i1, j0, j1;
-  bool a0, a1, b0, b1, any;
-};
-
-__device__ __forceinline__ Corners corners(int y0, int y1, int x0, int x1, int oy, int ox, int h, int w) {
-  Corners q;
-  q.i0 = y0 - oy; q.i1 = y1 - oy; q.j0 = x0 - ox; q.j1 = x1 - ox;
-  q.a0 = (unsigned)q.i0 < (unsigned)h; q.a1 = (unsigned)q.i1 < (unsigned)h;
-  q.b0 = (unsigned)q.j0 < (unsigned)w; q.b1 = (unsigned)q.j1 < (unsigned)w;
-  q.any = (q.a0 || q.a1) && (q.b0 || q.b1);
-  return q;
-}
-
-__device__ __forceinline__ double resized_canvas(const float* __restrict__ s, int sw, const Corners& q, double ly, double lx) {
-  const double v00 = q.a0 && q.b0 ? (double)s[q.i0 * sw + q.j0] : 0.0, v01 = q.a0 && q.b1 ? (double)s[q.i0 * sw + q.j1] : 0.0;
-  const double v10 = q.a1 && q.b0 ? (double)s[q.i1 * sw + q.j0] : 0.0, v11 = q.a1 && q.b1 ? (double)s[q.i1 * sw + q.j1] : 0.0;
-  return bilinear(v00, v01, v10, v11, ly, lx);
-}
-
-// losses.py:8-50 for one pixel: the end-point error against the rescaled prediction and torch's cosine_similarity
+// losses.py:8-50 for one pixel: the end-point error against the rescaled prediction, the cosine with the prediction as it is
 __device__ __forceinline__ void pixel_metrics(const double g[3], double fu, double fv, double scale_u, double scale_v, double* sum) {
-  const double du = g[0] - fu * scale_u, dv = g[1] - fv * scale_v;
-  const double epe = sqrt(du * du + dv * dv);
-  const double ng = fmax(sqrt(g[0] * g[0] + g[1] * g[1]), 1e-8), nf = fmax(sqrt(fu * fu + fv * fv), 1e-8);
-  const double cs = (g[0] / ng) * (fu / nf) + (g[1] / ng) * (fv / nf);
+  double epe, cs;
+  epe_cos(g[0] - fu * scale_u, g[1] - fv * scale_v, g[0], g[1], fu, fv, epe, cs);
   sum[0] += epe * g[2];
   sum[1] += cs * g[2];
   sum[2] += g[2];
@@ -145,31 +123,23 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __res
   const double scale_u = (double)Wg / (double)W, scale_v = (double)Hg / (double)H;     // losses.py:27
   double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
-    const int yg = (int)(p / Wg), xg = (int)(p - (long)yg * Wg);
-    int y0, y1, x0, x1;
-    double ly, lx;
-    bilinear_source(yg, sy, H, y0, y1, ly);
-    bilinear_source(xg, sx, W, x0, x1, lx);
-    const long r0 = (long)y0 * W, r1 = (long)y1 * W;
-    const double pu = bilinear((double)cu[r0 + x0], (double)cu[r0 + x1], (double)cu[r1 + x0], (double)cu[r1 + x1], ly, lx);
-    const double pv = bilinear((double)cv[r0 + x0], (double)cv[r0 + x1], (double)cv[r1 + x0], (double)cv[r1 + x1], ly, lx);
-    const double qu = bilinear((double)au[r0 + x0], (double)au[r0 + x1], (double)au[r1 + x0], (double)au[r1 + x1], ly, lx);
-    const double qv = bilinear((double)av[r0 + x0], (double)av[r0 + x1], (double)av[r1 + x0], (double)av[r1 + x1], ly, lx);
+    const FlowTaps s = flow_taps(p, Wg, sy, sx, H, W);
+    const double pu = sample(cu, s), pv = sample(cv, s), qu = sample(au, s), qv = sample(av, s);
     double g[3] = {(double)gk[p], (double)gk[HWg + p], (double)gk[2 * HWg + p]};
     if (mr != nullptr) {                                                          // test_patch.py:430-446: occluded by the moved patch
-      const Corners q = corners(y0, y1, x0, x1, yr, xr, hr, wr);
+      const Corners q = corners(s.y0, s.y1, s.x0, s.x1, yr, xr, hr, wr);
       if (q.any) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) g[c] = (1.0 - resized_canvas(mr + c * plane, sw, q, ly, lx)) * g[c];
+        for (int c = 0; c < 3; ++c) g[c] = (1.0 - resized_canvas(mr + c * plane, sw, q, s.ly, s.lx)) * g[c];
       }
     }
     double ga[3] = {g[0], g[1], g[2]};
-    const Corners q = corners(y0, y1, x0, x1, yt, xt, ht, wt);
+    const Corners q = corners(s.y0, s.y1, s.x0, s.x1, yt, xt, ht, wt);
     if (q.any) {
       double f[3] = {0.0, 0.0, patch_flow == 1 ? 1.0 : 0.0};
       if (patch_flow == 2) {
         // scipy.ndimage.zoom, order 1, mode='constant' (placement.hip): a source outside [0, n - 1] on either axis gives 0
-        const double cy = zy * (double)yg, cx = zx * (double)xg;
+        const double cy = zy * (double)s.yg, cx = zx * (double)s.xg;
         if (!(cy < 0.0 || cy > (double)(H - 1) || cx < 0.0 || cx > (double)(W - 1))) {
           const int fy0 = (int)floor(cy), fx0 = (int)floor(cx);
           const double ty = cy - (double)fy0, tx = cx - (double)fx0;
@@ -179,11 +149,11 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __res
           if (z.any) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-              const float* __restrict__ s = fl + c * plane;
-              double v = (z.a0 && z.b0 ? (double)s[z.i0 * sw + z.j0] : 0.0) * (wy0 * wx0);
-              v += (z.a0 && z.b1 ? (double)s[z.i0 * sw + z.j1] : 0.0) * (wy0 * wx1);
-              v += (z.a1 && z.b0 ? (double)s[z.i1 * sw + z.j0] : 0.0) * (wy1 * wx0);
-              v += (z.a1 && z.b1 ? (double)s[z.i1 * sw + z.j1] : 0.0) * (wy1 * wx1);
+              const float* __restrict__ fc = fl + c * plane;
+              double v = (z.a0 && z.b0 ? (double)fc[z.i0 * sw + z.j0] : 0.0) * (wy0 * wx0);
+              v += (z.a0 && z.b1 ? (double)fc[z.i0 * sw + z.j1] : 0.0) * (wy0 * wx1);
+              v += (z.a1 && z.b0 ? (double)fc[z.i1 * sw + z.j0] : 0.0) * (wy1 * wx0);
+              v += (z.a1 && z.b1 ? (double)fc[z.i1 * sw + z.j1] : 0.0) * (wy1 * wx1);
               f[c] = v;
             }
           }
@@ -191,17 +161,14 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __res
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const double m = resized_canvas(mt + c * plane, sw, q, ly, lx);
+        const double m = resized_canvas(mt + c * plane, sw, q, s.ly, s.lx);
         ga[c] = (1.0 - m) * g[c] + m * f[c];                                      // test_patch.py:455-457
       }
     }
     pixel_metrics(g, pu, pv, scale_u, scale_v, sum);
     pixel_metrics(ga, qu, qv, scale_u, scale_v, sum + 3);
   }
-  for (int q = 0; q < kSums; ++q) {
-    const double t = block_sum<kBlock>(sum[q], lds);
-    if (threadIdx.x == 0) part[((long)k * kSlots + blockIdx.x) * kSums + q] = t;
-  }
+  ufr::dev::store_partial<kBlock, kSums>(sum, lds, part, k, kSlots);
 }
 
 // grid K: one workgroup adds the `slots` partials of its item in a fixed order
@@ -210,8 +177,7 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_finalize_kernel(const dou
   __shared__ double lds[kBlock / 64];
   const int k = blockIdx.x;
   double t[kSums];
-  for (int q = 0; q < kSums; ++q)
-    t[q] = block_sum<kBlock>((int)threadIdx.x < slots ? part[((long)k * kSlots + threadIdx.x) * kSums + q] : 0.0, lds);
+  ufr::dev::item_totals<kBlock, kSums>(part, k, kSlots, slots, lds, t);
   if (threadIdx.x == 0) {
     const double den = t[2] + 1e-8, den_adv = t[5] + 1e-8;                        // losses.py:22
     out[4 * k] = (float)(t[0] / den);                                             // epe, adv_epe, cos_sim, adv_cos_sim
@@ -234,8 +200,6 @@ int check_places(const char* what, const int* places_host, int K, int records, i
   return UFR_OK;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int ufr_eval_paste(const float* tgt, const float* ref, const float* p_tgt, const float* m_tgt, const float* p_ref,
@@ -253,7 +217,7 @@ extern "C" int ufr_eval_paste(const float* tgt, const float* ref, const float* p
   if (!second) { p_ref = p_tgt; m_ref = m_tgt; }
   hipStream_t st = ufr::as_stream(stream);
   const long total = (long)K * 3 * H * W;
-  if (W % 4 == 0 && aligned16(tgt) && aligned16(ref) && aligned16(adv_tgt) && aligned16(adv_ref))
+  if (W % 4 == 0 && aligned16(tgt, ref, adv_tgt, adv_ref))
     eval_paste_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(tgt, ref, p_tgt, m_tgt, p_ref, m_ref, places, second,
                                                                                adv_tgt, adv_ref, total / 4, H, W, sh, sw, lo, hi);
   else
@@ -276,15 +240,11 @@ extern "C" int ufr_eval_metrics(const float* pred_clean, const float* pred_adv, 
   UFR_REQUIRE((long)H * W < (1L << 30) && (long)Hg * Wg < (1L << 30) && (long)K * 3 * sh * sw < (1L << 30),
               "eval metrics: too many pixels");
   UFR_REQUIRE(ignore_mask_flow == 0 || ignore_mask_flow == 1, "eval metrics: ignore_mask_flow = %d (0 or 1)", ignore_mask_flow);
-  UFR_REQUIRE(row0 >= 0 && rows > 0 && (long)row0 + K <= rows, "eval metrics: rows %d .. %ld leave the result buffer of %d rows", row0,
-              (long)row0 + K - 1, rows);
-  UFR_REQUIRE(ws_elems >= ufr_eval_metrics_workspace_doubles(K), "eval metrics: workspace of %ld doubles, %ld needed", ws_elems,
-              ufr_eval_metrics_workspace_doubles(K));
+  if (int rc = ufr::check_result_rows("eval metrics", row0, K, rows)) return rc;
+  if (int rc = ufr::check_workspace("eval metrics", ws_elems, ufr_eval_metrics_workspace_doubles(K))) return rc;
   if (int rc = check_places("eval metrics", places_host, K, m_ref != nullptr ? 2 : 1, H, W, sh, sw)) return rc;
   hipStream_t st = ufr::as_stream(stream);
-  const long npix = (long)Hg * Wg;
-  int slots = ufr::ceil_div(npix, kBlock);
-  if (slots > kSlots) slots = kSlots;
+  const int slots = ufr::metric_slots((long)Hg * Wg, kBlock);
   const int patch_flow = flow != nullptr ? 2 : (ignore_mask_flow ? 0 : 1);
   const double zy = Hg > 1 ? (double)(H - 1) / (double)(Hg - 1) : 1.0, zx = Wg > 1 ? (double)(W - 1) / (double)(Wg - 1) : 1.0;
   eval_metrics_kernel<<<dim3(slots, K), kBlock, 0, st>>>(pred_clean, pred_adv, gt, m_tgt, m_ref, flow, places, H, W, Hg, Wg, sh, sw,

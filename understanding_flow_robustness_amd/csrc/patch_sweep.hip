@@ -4,22 +4,21 @@
 //   ufr_sweep_paste    the K adversarial pairs from the one clean pair -- as canvases [K,3,H,W], or, for the windowed prefix, only
 //                      the window around each position's patch (the window table of ufr_cone_window first, then the windows);
 //   ufr_sweep_metrics  resized prediction, resized canvas mask, blended ground truth, both metrics and their weighted means in one
-//                      pass over the ground-truth pixels; float64 throughout, workgroup partials + a finalize launch (the pattern of
-//                      train_loss.hip): no float atomics, two runs are bit-identical.
+//                      pass over the ground-truth pixels; float64 throughout, the per-item metrics scheme of ufr_common.h.
 // The reference does, per position: three canvas-sized host arrays, one H2D copy, five torch operators for the paste, a bilinear
 // resize of the mask, five for the blend, two metric calls that each end in `.item()`.
 #include <climits>
-#include <cstdint>
 
 #include "ufr_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSlots = 128;            // workgroups (= partials) per position at most
+constexpr int kSlots = ufr::kMetricSlots;
 constexpr int kSums = 3;               // valid * epe, valid * cos, valid
 constexpr int kWinInts = 8;            // win[k] = {y0, x0, need_h, need_w, ymin, ymax, xmin, xmax} (window.hip)
 
+using ufr::aligned16;
 using ufr::dev::cone_axis;
 using ufr::dev::paste_clamped;      // attack.hip's paste_placed_kernel, do_clamp = 1
 
@@ -163,10 +162,13 @@ __global__ __launch_bounds__(kBlock) void sweep_paste_window_kernel(const float*
 }
 
 // ---- metrics ------------------------------------------------------------------------------------------------------------------
-using ufr::dev::block_sum;          // the sum over the workgroup in a fixed order, returned to every thread
-
-using ufr::dev::bilinear;           // torch's upsample_bilinear2d, align_corners = False, in float64
-using ufr::dev::bilinear_source;
+using ufr::dev::Corners;            // the canvas mask at the prediction's taps
+using ufr::dev::corners;
+using ufr::dev::epe_cos;
+using ufr::dev::FlowTaps;           // torch's upsample_bilinear2d, align_corners = False, in float64
+using ufr::dev::flow_taps;
+using ufr::dev::resized_canvas;
+using ufr::dev::sample;
 
 // grid (slots, K): workgroup (s, k) walks the ground-truth pixels s * 256 + t, + slots * 256, ... of position k
 __global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -184,44 +186,27 @@ __global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __re
   if (mask_p != nullptr) { oy = origins[2 * k]; ox = origins[2 * k + 1]; }
   double sum[kSums] = {0.0, 0.0, 0.0};
   for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
-    const int yg = (int)(p / Wg), xg = (int)(p - (long)yg * Wg);
-    int y0, y1, x0, x1;
-    double ly, lx;
-    bilinear_source(yg, sy, H, y0, y1, ly);
-    bilinear_source(xg, sx, W, x0, x1, lx);
-    const long r0 = (long)y0 * W, r1 = (long)y1 * W;
-    const double fu = bilinear((double)pu[r0 + x0], (double)pu[r0 + x1], (double)pu[r1 + x0], (double)pu[r1 + x1], ly, lx);
-    const double fv = bilinear((double)pv[r0 + x0], (double)pv[r0 + x1], (double)pv[r1 + x0], (double)pv[r1 + x1], ly, lx);
+    const FlowTaps s = flow_taps(p, Wg, sy, sx, H, W);
+    const double fu = sample(pu, s), fv = sample(pv, s);
     double g[3] = {(double)gt[p], (double)gt[HWg + p], (double)gt[2 * HWg + p]};
     if (mask_p != nullptr) {
       // the canvas mask at the (already clamped) source rows / columns: mask_p inside the rectangle, 0 outside
-      const int i0 = y0 - oy, i1 = y1 - oy, j0 = x0 - ox, j1 = x1 - ox;
-      const bool a0 = (unsigned)i0 < (unsigned)ph, a1 = (unsigned)i1 < (unsigned)ph;
-      const bool b0 = (unsigned)j0 < (unsigned)pw, b1 = (unsigned)j1 < (unsigned)pw;
-      if ((a0 || a1) && (b0 || b1)) {
+      const Corners q = corners(s.y0, s.y1, s.x0, s.x1, oy, ox, ph, pw);
+      if (q.any) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const float* __restrict__ mc = mask_p + (long)c * ph * pw;
-          const double m00 = a0 && b0 ? (double)mc[i0 * pw + j0] : 0.0, m01 = a0 && b1 ? (double)mc[i0 * pw + j1] : 0.0;
-          const double m10 = a1 && b0 ? (double)mc[i1 * pw + j0] : 0.0, m11 = a1 && b1 ? (double)mc[i1 * pw + j1] : 0.0;
-          const double m = bilinear(m00, m01, m10, m11, ly, lx);
+          const double m = resized_canvas(mask_p + (long)c * ph * pw, pw, q, s.ly, s.lx);
           g[c] = (1.0 - m) * g[c] + m * (c == 2 ? patch_valid : 0.0);            // test_moving_patch.py:430-432
         }
       }
     }
-    const double du = g[0] - fu * scale_u, dv = g[1] - fv * scale_v;              // losses.py:29-30
-    const double epe = sqrt(du * du + dv * dv);
-    // torch.nn.functional.cosine_similarity: each vector divided by max(its norm, eps) first, then the dot product
-    const double ng = fmax(sqrt(g[0] * g[0] + g[1] * g[1]), 1e-8), nf = fmax(sqrt(fu * fu + fv * fv), 1e-8);
-    const double cs = (g[0] / ng) * (fu / nf) + (g[1] / ng) * (fv / nf);
+    double epe, cs;                                                               // losses.py:29-30: the error against the rescaled
+    epe_cos(g[0] - fu * scale_u, g[1] - fv * scale_v, g[0], g[1], fu, fv, epe, cs);  // prediction, the cosine with it as it is
     sum[0] += epe * g[2];
     sum[1] += cs * g[2];
     sum[2] += g[2];
   }
-  for (int q = 0; q < kSums; ++q) {
-    const double t = block_sum<kBlock>(sum[q], lds);
-    if (threadIdx.x == 0) part[((long)k * kSlots + blockIdx.x) * kSums + q] = t;
-  }
+  ufr::dev::store_partial<kBlock, kSums>(sum, lds, part, k, kSlots);
 }
 
 // grid K: one workgroup adds the `slots` partials of its position in a fixed order
@@ -230,8 +215,7 @@ __global__ __launch_bounds__(kBlock) void sweep_metrics_finalize_kernel(const do
   __shared__ double lds[kBlock / 64];
   const int k = blockIdx.x;
   double t[kSums];
-  for (int q = 0; q < kSums; ++q)
-    t[q] = block_sum<kBlock>((int)threadIdx.x < slots ? part[((long)k * kSlots + threadIdx.x) * kSums + q] : 0.0, lds);
+  ufr::dev::item_totals<kBlock, kSums>(part, k, kSlots, slots, lds, t);
   if (threadIdx.x == 0) {
     const double den = t[2] + 1e-8;                                               // losses.py:22
     out[2 * k] = (float)(t[0] / den);
@@ -247,8 +231,6 @@ int check_origins(const char* what, const int* origins_host, int K, int H, int W
                 origins_host[2 * k + 1], ph, pw, H, W);
   return UFR_OK;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -267,7 +249,7 @@ extern "C" int ufr_sweep_paste(const float* tgt, const float* ref, const float* 
     UFR_REQUIRE(chain == nullptr && xw == nullptr, "sweep paste: a chain or window stack without the window table");
     UFR_REQUIRE(adv_tgt && adv_ref, "sweep paste: null pointer argument (canvas form: adv_tgt, adv_ref)");
     const long total = (long)K * 3 * H * W;
-    if (W % 4 == 0 && aligned16(tgt) && aligned16(ref) && aligned16(adv_tgt) && aligned16(adv_ref))
+    if (W % 4 == 0 && aligned16(tgt, ref, adv_tgt, adv_ref))
       sweep_paste_canvas_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(tgt, ref, patch_p, mask_p, origins, adv_tgt,
                                                                                          adv_ref, total / 4, H, W, ph, pw, lo, hi);
     else
@@ -295,7 +277,7 @@ extern "C" int ufr_sweep_paste(const float* tgt, const float* ref, const float* 
   if (int rc = ufr::launched("sweep_window_table_kernel")) return rc;
   const long total = (long)K * 3 * win_h * win_w;
   // a window's first column is a multiple of the chain stride, or W - win_w when the clamp holds it inside the frame
-  if (W % 4 == 0 && win_w % 4 == 0 && stride % 4 == 0 && aligned16(tgt) && aligned16(ref) && aligned16(xw))
+  if (W % 4 == 0 && win_w % 4 == 0 && stride % 4 == 0 && aligned16(tgt, ref, xw))
     sweep_paste_window_kernel<4><<<ufr::stream_grid(total / 4, kBlock), kBlock, 0, st>>>(tgt, ref, patch_p, mask_p, origins, win, xw,
                                                                                        total / 4, K, H, W, win_h, win_w, ph, pw, lo, hi);
   else
@@ -314,10 +296,8 @@ extern "C" int ufr_sweep_metrics(const float* pred, const float* gt, const float
               W, Hg, Wg);
   UFR_REQUIRE((long)H * W < (1L << 30) && (long)Hg * Wg < (1L << 30), "sweep metrics: too many pixels");
   UFR_REQUIRE(valid_in_patch == 0 || valid_in_patch == 1, "sweep metrics: valid_in_patch = %d (0 or 1)", valid_in_patch);
-  UFR_REQUIRE(row0 >= 0 && rows > 0 && (long)row0 + K <= rows, "sweep metrics: rows %d .. %ld leave the result buffer of %d rows", row0,
-              (long)row0 + K - 1, rows);
-  UFR_REQUIRE(ws_elems >= ufr_sweep_metrics_workspace_doubles(K), "sweep metrics: workspace of %ld doubles, %ld needed", ws_elems,
-              ufr_sweep_metrics_workspace_doubles(K));
+  if (int rc = ufr::check_result_rows("sweep metrics", row0, K, rows)) return rc;
+  if (int rc = ufr::check_workspace("sweep metrics", ws_elems, ufr_sweep_metrics_workspace_doubles(K))) return rc;
   if (mask_p != nullptr) {
     UFR_REQUIRE(origins && origins_host, "sweep metrics: null pointer argument (a patch needs its origins, on the device and the host)");
     UFR_REQUIRE(ph > 0 && pw > 0, "sweep metrics: bad shape ph=%d pw=%d", ph, pw);
@@ -326,9 +306,7 @@ extern "C" int ufr_sweep_metrics(const float* pred, const float* gt, const float
     if (int rc = check_origins("sweep metrics", origins_host, K, H, W, ph, pw)) return rc;
   }
   hipStream_t st = ufr::as_stream(stream);
-  const long npix = (long)Hg * Wg;
-  int slots = ufr::ceil_div(npix, kBlock);
-  if (slots > kSlots) slots = kSlots;
+  const int slots = ufr::metric_slots((long)Hg * Wg, kBlock);
   sweep_metrics_kernel<<<dim3(slots, K), kBlock, 0, st>>>(pred, gt, mask_p, origins, H, W, Hg, Wg, ph, pw, (double)valid_in_patch, ws);
   if (int rc = ufr::launched("sweep_metrics_kernel")) return rc;
   sweep_metrics_finalize_kernel<<<K, kBlock, 0, st>>>(ws, slots, out + 2L * row0);

@@ -83,10 +83,7 @@ __global__ __launch_bounds__(256) void raft_context_split_bwd_kernel(const V* __
   }
 }
 
-inline bool aligned16(const void* a, const void* b, const void* c, const void* d = nullptr, const void* e = nullptr) {
-  return ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c) | reinterpret_cast<size_t>(d) |
-           reinterpret_cast<size_t>(e)) & 15) == 0;
-}
+using ufr::aligned16;
 
 }  // namespace
 

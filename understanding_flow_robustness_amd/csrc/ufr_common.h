@@ -4,6 +4,7 @@
 
 #include <climits>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 
 #include "../../include/ufr_hip.h"
@@ -49,6 +50,32 @@ inline int stream_grid(long n, int block) {
   if (g > 2048) g = 2048;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+// 16-byte alignment of every pointer given: the test in front of each float4 / bf16x8 kernel form
+template <class... P>
+inline bool aligned16(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
+
+// ---- per-item metrics: the ONE scheme of ufr_sweep_metrics, ufr_eval_metrics, ufr_global_metrics and ufr_validation_metrics ---------
+// A grid of (slots, K) workgroups of 256 threads, slots = metric_slots(work of one item, 256): workgroup (s, k) walks the elements
+// s * 256 + t, + slots * 256, ... of item k with float64 sums per thread, `dev::store_partial` reduces them (block_sum) into the
+// workgroup's partial in the workspace, and a finalize launch of K workgroups adds the `slots` partials of its item, thread t < slots
+// partial t (`dev::item_totals`).  slots follows from the sizes alone, so every sum has a fixed order: no float atomics, two runs are
+// bit-identical.  The workspace holds `stride` partials per item: kMetricSlots (sweep, eval, global) or slots itself (validation).
+constexpr int kMetricSlots = 128;   // workgroups (= partials) per item at most
+inline int metric_slots(long work, int block) {
+  const int s = ceil_div(work, block);
+  return s > kMetricSlots ? kMetricSlots : s;
+}
+// the two checks every metrics entry makes of its result rows and its workspace; `what` is the entry's name in its messages
+inline int check_result_rows(const char* what, int row0, int K, int rows) {
+  if (!(row0 >= 0 && rows > 0 && (long)row0 + K <= rows))
+    return fail(UFR_EINVAL, "%s: rows %d .. %ld leave the result buffer of %d rows", what, row0, (long)row0 + K - 1, rows);
+  return UFR_OK;
+}
+inline int check_workspace(const char* what, long ws_elems, long need) {
+  if (!(ws_elems >= need)) return fail(UFR_EINVAL, "%s: workspace of %ld doubles, %ld needed", what, ws_elems, need);
+  return UFR_OK;
 }
 
 // correlation_vec.hip: 0 = launched, 1 = shape not covered (use the general fast path), <0 = error
@@ -157,7 +184,26 @@ __device__ inline double block_sum(double v, double* lds) {
   return t;
 }
 
-// ---- shared by patch_sweep.hip and patch_eval.hip ---------------------------------------------------------------------------------
+// the per-item metrics scheme (above): the partial of workgroup (blockIdx.x, k) is WIDTH doubles, the first N of them sums.
+// store_partial: this thread's N sums -> the workgroup's partial, which is returned (thread 0 may add to it)
+template <int BLOCK, int N, int WIDTH = N>
+__device__ inline double* store_partial(const double* sum, double* lds, double* __restrict__ part, int k, int stride) {
+  double* __restrict__ mine = part + ((long)k * stride + blockIdx.x) * WIDTH;
+  for (int q = 0; q < N; ++q) {
+    const double t = block_sum<BLOCK>(sum[q], lds);
+    if (threadIdx.x == 0) mine[q] = t;
+  }
+  return mine;
+}
+// item_totals: t[0..N) = the sums over the `slots` partials of item k, thread i < slots adding partial i (every thread gets them)
+template <int BLOCK, int N, int WIDTH = N>
+__device__ inline void item_totals(const double* __restrict__ part, int k, int stride, int slots, double* lds, double* t) {
+  const bool mine = (int)threadIdx.x < slots;
+  const double* __restrict__ p = part + ((long)k * stride + (mine ? threadIdx.x : 0)) * WIDTH;
+  for (int q = 0; q < N; ++q) t[q] = block_sum<BLOCK>(mine ? p[q] : 0.0, lds);
+}
+
+// ---- shared by patch_sweep.hip, patch_eval.hip and global_eval.hip -------------------------------------------------------------------
 // attack.hip's paste_placed_kernel, do_clamp = 1: (1-m)*img and m*patch are rounded separately, then added (no fma)
 __device__ __forceinline__ float paste_clamped(float img, float m, float pv, float lo, float hi) {
   const float mp = m * pv, om = 1.0f - m;
@@ -177,6 +223,57 @@ __device__ __forceinline__ void bilinear_source(int dst, double scale, int in, i
 __device__ __forceinline__ double bilinear(double v00, double v01, double v10, double v11, double ly, double lx) {
   const double hy = 1.0 - ly, hx = 1.0 - lx;
   return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
+// Ground-truth pixel p = yg * Wg + xg of an Hg x Wg grid -> the four taps of an H x W prediction resized to it (sy = H / Hg,
+// sx = W / Wg): rows y0 / y1 at offsets r0 / r1, columns x0 / x1, weights ly / lx of the second row / column
+struct FlowTaps {
+  int yg, xg, y0, y1, x0, x1;
+  double ly, lx;
+  long r0, r1;
+};
+__device__ __forceinline__ FlowTaps flow_taps(long p, int Wg, double sy, double sx, int H, int W) {
+  FlowTaps s;
+  s.yg = (int)(p / Wg);
+  s.xg = (int)(p - (long)s.yg * Wg);
+  bilinear_source(s.yg, sy, H, s.y0, s.y1, s.ly);
+  bilinear_source(s.xg, sx, W, s.x0, s.x1, s.lx);
+  s.r0 = (long)s.y0 * W;
+  s.r1 = (long)s.y1 * W;
+  return s;
+}
+// one plane of the prediction at those taps
+__device__ __forceinline__ double sample(const float* __restrict__ f, const FlowTaps& s) {
+  return bilinear((double)f[s.r0 + s.x0], (double)f[s.r0 + s.x1], (double)f[s.r1 + s.x0], (double)f[s.r1 + s.x1], s.ly, s.lx);
+}
+
+// One pixel: the length of (du, dv), the error vector as the caller's reference forms it (losses.py:29-30: ground truth - rescaled
+// prediction; perturb_model.py:46-47: rescaled prediction - ground truth), and torch's cosine_similarity of (gu, gv) and (fu, fv):
+// each vector divided by max(its norm, eps) first, then the dot product
+__device__ __forceinline__ void epe_cos(double du, double dv, double gu, double gv, double fu, double fv, double& epe, double& cs) {
+  epe = sqrt(du * du + dv * dv);
+  const double ng = fmax(sqrt(gu * gu + gv * gv), 1e-8), nf = fmax(sqrt(fu * fu + fv * fv), 1e-8);
+  cs = (gu / ng) * (fu / nf) + (gv / ng) * (fv / nf);
+}
+
+// A canvas that is 0 outside an h x w rectangle at (oy, ox) of the frame and `s` (rows of sw floats) inside it, at frame rows
+// y0 / y1 and columns x0 / x1 (already inside the frame): which taps fall into the rectangle, and the canvas resized at them
+struct Corners {
+  int i0, i1, j0, j1;
+  bool a0, a1, b0, b1, any;
+};
+__device__ __forceinline__ Corners corners(int y0, int y1, int x0, int x1, int oy, int ox, int h, int w) {
+  Corners q;
+  q.i0 = y0 - oy; q.i1 = y1 - oy; q.j0 = x0 - ox; q.j1 = x1 - ox;
+  q.a0 = (unsigned)q.i0 < (unsigned)h; q.a1 = (unsigned)q.i1 < (unsigned)h;
+  q.b0 = (unsigned)q.j0 < (unsigned)w; q.b1 = (unsigned)q.j1 < (unsigned)w;
+  q.any = (q.a0 || q.a1) && (q.b0 || q.b1);
+  return q;
+}
+__device__ __forceinline__ double resized_canvas(const float* __restrict__ s, int sw, const Corners& q, double ly, double lx) {
+  const double v00 = q.a0 && q.b0 ? (double)s[q.i0 * sw + q.j0] : 0.0, v01 = q.a0 && q.b1 ? (double)s[q.i0 * sw + q.j1] : 0.0;
+  const double v10 = q.a1 && q.b0 ? (double)s[q.i1 * sw + q.j0] : 0.0, v11 = q.a1 && q.b1 ? (double)s[q.i1 * sw + q.j1] : 0.0;
+  return bilinear(v00, v01, v10, v11, ly, lx);
 }
 
 }  // namespace dev

@@ -5,19 +5,16 @@
 //                           torch on this device;
 //   ufr_validation_metrics  crops the padded-frame prediction in place and reduces the per-pixel errors of the three validators to
 //                           eight float64 values per item: float32 per pixel with every operation rounded on its own (what the
-//                           reference's threshold comparisons see), float64 sums, workgroup partials + a finalize launch (the
-//                           pattern of global_eval.hip): no float atomics, two runs are bit-identical.
-#include <cstdint>
-
+//                           reference's threshold comparisons see), float64 sums, the per-item metrics scheme of ufr_common.h
+//                           with `slots` partials per item in the workspace.
 #include "ufr_common.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kSlots = 128;            // workgroups (= partials) per item at most
 constexpr int kCols = 8;               // UFR_VALIDATION_COLS
 
-using ufr::dev::block_sum;
+using ufr::aligned16;
 
 // torch's device kernel for `x / 255.0` (a host scalar divisor) multiplies by the float32 reciprocal
 __device__ __forceinline__ float scaled(float v, float inv) { return v * inv; }
@@ -111,11 +108,7 @@ __global__ __launch_bounds__(kBlock) void validation_metrics_kernel(const float*
       entry(sqrtf(dv2), mag, val, sum);
     }
   }
-  double* __restrict__ mine = part + ((long)k * gridDim.x + blockIdx.x) * kCols;
-  for (int q = 0; q < kCols; ++q) {
-    const double t = block_sum<kBlock>(sum[q], lds);
-    if (threadIdx.x == 0) mine[q] = t;
-  }
+  ufr::dev::store_partial<kBlock, kCols>(sum, lds, part, k, gridDim.x);
 }
 
 // grid K: one workgroup adds the `slots` partials of its item in a fixed order
@@ -123,19 +116,10 @@ __global__ __launch_bounds__(kBlock) void validation_metrics_finalize_kernel(con
                                                                              double* __restrict__ out) {
   __shared__ double lds[kBlock / 64];
   const int k = blockIdx.x;
-  const bool mine = (int)threadIdx.x < slots;
-  const double* __restrict__ p = part + ((long)k * slots + (mine ? threadIdx.x : 0)) * kCols;
-  for (int q = 0; q < kCols; ++q) {
-    const double t = block_sum<kBlock>(mine ? p[q] : 0.0, lds);
-    if (threadIdx.x == 0) out[(long)k * kCols + q] = t;
-  }
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int metric_slots(int H, int W) {
-  const int s = ufr::ceil_div((long)H * W, kBlock);
-  return s > kSlots ? kSlots : s;
+  double t[kCols];
+  ufr::dev::item_totals<kBlock, kCols>(part, k, slots, slots, lds, t);
+  if (threadIdx.x == 0)
+    for (int q = 0; q < kCols; ++q) out[(long)k * kCols + q] = t[q];
 }
 
 template <int V>
@@ -162,8 +146,8 @@ extern "C" int ufr_validation_pad(const float* image1, const float* image2, floa
   UFR_REQUIRE((long)Hp * Wp <= (1L << 40) / 3 / K, "validation pad: too many pixels");
   hipStream_t st = ufr::as_stream(stream);
   const long total = (long)K * 3 * Hp * Wp;
-  if (Wp % 4 == 0 && aligned16(out1) && aligned16(out2)) {
-    const int src4 = W % 4 == 0 && left % 4 == 0 && aligned16(image1) && aligned16(image2) ? 1 : 0;
+  if (Wp % 4 == 0 && aligned16(out1, out2)) {
+    const int src4 = W % 4 == 0 && left % 4 == 0 && aligned16(image1, image2) ? 1 : 0;
     launch_pad<4>(divide_by_255 != 0, image1, image2, out1, out2, total / 4, H, W, Hp, Wp, top, left, src4, st);
   } else {
     launch_pad<1>(divide_by_255 != 0, image1, image2, out1, out2, total, H, W, Hp, Wp, top, left, 0, st);
@@ -173,7 +157,7 @@ extern "C" int ufr_validation_pad(const float* image1, const float* image2, floa
 
 extern "C" long ufr_validation_metrics_workspace_doubles(int K, int H, int W) {
   if (K < 1 || H < 1 || W < 1 || (long)H * W >= (1L << 29)) return -1;
-  return (long)K * metric_slots(H, W) * kCols;
+  return (long)K * ufr::metric_slots((long)H * W, kBlock) * kCols;
 }
 
 extern "C" int ufr_validation_metrics(const float* pred, const float* gt, const float* valid, int K, int Hp, int Wp, int top, int left,
@@ -187,12 +171,10 @@ extern "C" int ufr_validation_metrics(const float* pred, const float* gt, const 
   UFR_REQUIRE((long)top + H <= Hp && (long)left + W <= Wp,
               "validation metrics: the crop of %d x %d at (%d, %d) leaves the padded frame of %d x %d", H, W, top, left, Hp, Wp);
   UFR_REQUIRE(mode >= 0 && mode <= 2, "validation metrics: mode %d (0 end-point, 1 per component, 2 channel 0 against both)", mode);
-  UFR_REQUIRE(row0 >= 0 && rows > 0 && (long)row0 + K <= rows, "validation metrics: rows %d .. %ld leave the result buffer of %d rows",
-              row0, (long)row0 + K - 1, rows);
-  UFR_REQUIRE(ws_elems >= ufr_validation_metrics_workspace_doubles(K, H, W), "validation metrics: workspace of %ld doubles, %ld needed",
-              ws_elems, ufr_validation_metrics_workspace_doubles(K, H, W));
+  if (int rc = ufr::check_result_rows("validation metrics", row0, K, rows)) return rc;
+  if (int rc = ufr::check_workspace("validation metrics", ws_elems, ufr_validation_metrics_workspace_doubles(K, H, W))) return rc;
   hipStream_t st = ufr::as_stream(stream);
-  const int slots = metric_slots(H, W);                          // from the sizes alone: it fixes the order of the sums
+  const int slots = ufr::metric_slots((long)H * W, kBlock);      // from the sizes alone: it fixes the order of the sums
   validation_metrics_kernel<<<dim3(slots, K), kBlock, 0, st>>>(pred, gt, valid, Hp, Wp, top, left, H, W, mode, ws);
   if (int rc = ufr::launched("validation_metrics_kernel")) return rc;
   validation_metrics_finalize_kernel<<<K, kBlock, 0, st>>>(ws, slots, out + (long)kCols * row0);

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from .chunked_eval import ChunkedEval, check_pair
 
 NAMES = ["noise0_L0", "noise0_L1", "noise1_L0", "noise1_L1", "epe_clean", "epe_adv", "l1_clean", "l1_adv", "cossim_clean",
          "cossim_adv"]
@@ -144,86 +145,66 @@ def refuse_out_of_scope(args, perturb_model=None):
                                   "the tensor as arbitrary_gt")
 
 
-class Chunks:
-    """Items waiting for their chunk, the chunk's forward and metrics launch, the results on the device."""
+class Chunks(ChunkedEval):
+    """The chunk's (apply,) forward and metrics launch (chunked_eval.py: the waiting items, the results on the device)."""
 
     def __init__(self, flow_net, args, chunk, arbitrary_gt=None, with_noise=True):
-        if int(chunk) < 1:
-            raise ValueError("chunk must be positive")
-        self.net, self.args, self.chunk = flow_net, args, int(chunk)
+        super().__init__(chunk)
+        self.net, self.args = flow_net, args
         self.any_gt, self.with_noise = arbitrary_gt, with_noise
-        self.waiting, self.results, self.any_results = [], [], []
-        self.ws = None
-        self.events = None               # tools/bench_global_eval.py: device events around the entries
-
-    def _mark(self, stage):
-        if self.events is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.events.append((stage, ev))
 
     def add(self, image0, image1, gt, noise=None, adv=None):
         """One item: noise = (n0, n1) [1,3,H,W] of this item with adv = its perturbed frames, or adv None and noise the fixed
         perturbation every item shares (then applied per chunk)."""
-        key = (tuple(image0.shape), tuple(gt.shape), adv is None)
-        if self.waiting and (self.waiting[0][0] != key or len(self.waiting) == self.chunk):
-            self.flush()
-        self.waiting.append((key, image0, image1, gt, noise, adv))
+        super().add((tuple(image0.shape), tuple(gt.shape), adv is None), image0, image1, gt, noise, adv)
 
     def _metrics(self, clean, advf, gt, n0, n1, K, Kn, H, W):
         lib = L.lib()
         dev = clean.device
-        if self.ws is None or self.ws.device != dev:
-            self.ws = torch.zeros(lib.ufr_global_metrics_workspace_doubles(self.chunk), dtype=torch.float64, device=dev)
+        ws = self.workspace(lib.ufr_global_metrics_workspace_doubles(self.chunk), dev)
         out = torch.zeros(K, len(NAMES), dtype=torch.float64, device=dev)
         opt = lambda t: L.ptr(t) if t is not None else None
         L.check(lib.ufr_global_metrics(L.ptr(clean), L.ptr(advf), L.ptr(gt), opt(n0), opt(n1), K, int(gt.shape[0]), Kn,
-                                       int(gt.shape[1]), H, W, int(gt.shape[2]), int(gt.shape[3]), L.ptr(self.ws), self.ws.numel(),
+                                       int(gt.shape[1]), H, W, int(gt.shape[2]), int(gt.shape[3]), L.ptr(ws), ws.numel(),
                                        L.ptr(out), 0, K, L.stream()), "global metrics")
         return out
 
-    def flush(self):
+    def run_chunk(self, items):
         """One chunk: (apply,) ONE forward of the clean and the perturbed pairs, metrics."""
         from .flownets.utils_model import predict_flow
-        if not self.waiting:
-            return
-        items, self.waiting = self.waiting, []
         K = len(items)
-        f32 = lambda ts: torch.cat([t.detach().to(torch.float32) for t in ts]).contiguous()
+        dev = items[0][1].device
+        f32 = lambda ts: self.stack_f32(ts, dev)
         img0, img1, gt = f32([it[1] for it in items]), f32([it[2] for it in items]), f32([it[3] for it in items])
         H, W = int(img0.shape[2]), int(img0.shape[3])
-        fixed = items[0][5] is None
-        with torch.no_grad():
-            self._mark("start")
-            if fixed:
-                n0, n1 = (n.detach().to(torch.float32).contiguous() for n in items[0][4])
-                adv0, adv1 = torch.empty_like(img0), torch.empty_like(img1)
-                L.check(L.lib().ufr_global_apply(L.ptr(img0), L.ptr(img1), L.ptr(n0), L.ptr(n1), L.ptr(adv0), L.ptr(adv1), K, 1, H, W,
-                                                 0.0, 1.0, L.stream()), "global apply")
-                Kn = 1
-            else:
-                n0, n1 = f32([it[4][0] for it in items]), f32([it[4][1] for it in items])
-                adv0, adv1 = f32([it[5][0] for it in items]), f32([it[5][1] for it in items])
-                Kn = K
-            self._mark("apply")
-            flows = predict_flow(self.net, None, torch.cat((img0, adv0)), torch.cat((img1, adv1)), self.args)
-            if flows.dim() != 4 or flows.shape[0] != 2 * K or flows.shape[1] != 2:
-                raise RuntimeError(f"the network returned a flow of shape {tuple(flows.shape)} for {2 * K} pairs of {H}x{W} frames")
-            flows = flows.to(torch.float32).contiguous()
-            Hp, Wp = int(flows.shape[2]), int(flows.shape[3])
-            self._mark("forward")
-            if not self.with_noise:
-                n0 = n1 = None
-            self.results.append(self._metrics(flows[:K], flows[K:], gt, n0, n1, K, Kn, Hp, Wp))
-            if self.any_gt is not None:
-                self.any_results.append(self._metrics(flows[:K], flows[K:], self.any_gt, None, None, K, 0, Hp, Wp))
-            self._mark("metrics")
+        self._mark("start")
+        if items[0][5] is None:              # the fixed perturbation
+            n0, n1 = (n.detach().to(torch.float32).contiguous() for n in items[0][4])
+            adv0, adv1 = torch.empty_like(img0), torch.empty_like(img1)
+            L.check(L.lib().ufr_global_apply(L.ptr(img0), L.ptr(img1), L.ptr(n0), L.ptr(n1), L.ptr(adv0), L.ptr(adv1), K, 1, H, W,
+                                             0.0, 1.0, L.stream()), "global apply")
+            Kn = 1
+        else:
+            n0, n1 = f32([it[4][0] for it in items]), f32([it[4][1] for it in items])
+            adv0, adv1 = f32([it[5][0] for it in items]), f32([it[5][1] for it in items])
+            Kn = K
+        self._mark("apply")
+        flows = predict_flow(self.net, None, torch.cat((img0, adv0)), torch.cat((img1, adv1)), self.args)
+        flows = self.checked_flow(flows, 2 * K, H, W).to(torch.float32).contiguous()
+        Hp, Wp = int(flows.shape[2]), int(flows.shape[3])
+        self._mark("forward")
+        if not self.with_noise:
+            n0 = n1 = None
+        out = self._metrics(flows[:K], flows[K:], gt, n0, n1, K, Kn, Hp, Wp)
+        if self.any_gt is not None:
+            out = (out, self._metrics(flows[:K], flows[K:], self.any_gt, None, None, K, 0, Hp, Wp))
+        self._mark("metrics")
+        return out
 
     def read(self):
         """The one host synchronisation: ([N,10], [N,10] against the arbitrary ground truth or None)."""
-        self.flush()
-        table = lambda rs: torch.cat(rs).cpu().numpy() if rs else np.zeros((0, len(NAMES)))
-        return table(self.results), (table(self.any_results) if self.any_gt is not None else None)
+        tables = super().read() or [np.zeros((0, len(NAMES)))] * 2
+        return tables[0], (tables[1] if self.any_gt is not None else None)
 
 
 def _unpack(data):
@@ -257,8 +238,7 @@ def evaluate_perturbation(flow_net, loader, args: Namespace, *, perturb_model=No
         raise ValueError("exactly one of perturb_model (a per-image attack) and noise (a fixed perturbation) is needed")
     if noise is not None:
         n0, n1 = noise
-        if n0.dim() != 4 or n0.shape[0] != 1 or n0.shape[1] != 3 or n1.shape != n0.shape:
-            raise ValueError("noise is (n0, n1), [1,3,H,W] each")
+        check_pair(n0, n1, "noise is (n0, n1), [1,3,H,W] each")
         L.require_hip(n0, "noise0", contiguous=False)
         L.require_hip(n1, "noise1", contiguous=False)
     if arbitrary_gt is not None:
@@ -270,23 +250,19 @@ def evaluate_perturbation(flow_net, loader, args: Namespace, *, perturb_model=No
         arbitrary_gt = arbitrary_gt.detach().to(torch.float32).contiguous()
     homogeneous = bool(getattr(args, "homogeneous", False))
     ev = Chunks(flow_net, args, chunk, arbitrary_gt)
-    ev.events = getattr(evaluate_perturbation, "_debug_events", None)
-    frozen, count = False, 0
+    ev.events = getattr(evaluate_perturbation, "_debug_events", None)     # tools/bench_global_eval.py: device events around the entries
+    count = 0
     for data in loader:
         image0, image1, gt, gt_down = _unpack(data)
         if homogeneous:
             image1, gt = image0, torch.zeros_like(gt)
-        if image0.dim() != 4 or image0.shape[0] != 1 or image0.shape[1] != 3 or image1.shape != image0.shape:
-            raise ValueError("the loader yields batch-1 items: image0 and image1 [1,3,H,W]")
+        check_pair(image0, image1, "the loader yields batch-1 items: image0 and image1 [1,3,H,W]")
         if gt.dim() != 4 or gt.shape[0] != 1 or gt.shape[1] not in (2, 3):
             raise ValueError("ground_truth must be [1,C,Hg,Wg] with C = 2 or 3")
         for t, name in ((image0, "image0"), (image1, "image1"), (gt, "ground_truth")):
             L.require_hip(t, name, contiguous=False)
-        if not frozen:
-            L.freeze_parameters(flow_net)
-            flow_net.eval()
-            frozen = True
-        with torch.cuda.device(image0.device):
+        ev.freeze_once(flow_net)
+        with torch.cuda.device(image0.device):          # the attack's; a chunk runs under the guard of its own items
             if perturb_model is not None:
                 target = arbitrary_gt if arbitrary_gt is not None else gt_down
                 if target is None:
@@ -301,9 +277,6 @@ def evaluate_perturbation(flow_net, loader, args: Namespace, *, perturb_model=No
         count += 1
         if homogeneous:
             break
-    if ev.waiting:
-        with torch.cuda.device(ev.waiting[0][1].device):
-            ev.flush()
     per_item, per_item_any = ev.read()
     res = GlobalEvalResult(per_item, list(NAMES), results_dict(per_item) if len(per_item) else {})
     if arbitrary_gt is not None:

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .chunked_eval import ChunkedEval, check_pair
 
 
 @dataclass
@@ -38,12 +39,14 @@ def _refuse_3d(what):
                               "calibration and poses); that projection is not part of this project")
 
 
-class _Evaluation:
-    """The state of one call: the float64 patch state, the items waiting for their chunk, the results."""
+class _Evaluation(ChunkedEval):
+    """The state of one call: the float64 patch state and the locations; the chunk's paste, forward and metrics launch
+    (chunked_eval.py: the waiting items, the results on the device)."""
 
     def __init__(self, flow_net, patch, mask, patch_shape, args, chunk):
         from .patch_attack import _pixel_range
-        self.net, self.args, self.chunk = flow_net, args, int(chunk)
+        super().__init__(chunk)
+        self.net, self.args = flow_net, args
         self.patch, self.mask, self.patch_shape = patch, mask, tuple(patch_shape)
         self.patch_d = self.mask_d = None
         self.lo, self.hi = _pixel_range(args.flownet)
@@ -53,15 +56,7 @@ class _Evaluation:
         self.ignore = 1 if getattr(args, "ignore_mask_flow", False) else 0
         self.square = getattr(args, "patch_type", "circle") == "square"
         self.fixed_loc = (int(getattr(args, "fixed_loc_x", -1)), int(getattr(args, "fixed_loc_y", -1)))
-        self.waiting, self.results, self.locations = [], [], []
-        self.ws = None
-        self.events = None               # tools/bench_patch_eval.py: device events around the two entries
-
-    def _mark(self, stage):
-        if self.events is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.events.append((stage, ev))
+        self.locations = []
 
     def _state(self, dev):
         if self.patch_d is None:
@@ -90,22 +85,15 @@ class _Evaluation:
         return pt.record_from_canvas(cp, cm, x, y, shape, slot)
 
     def add(self, tgt, ref, gt, rec):
-        key = (tuple(tgt.shape), tuple(gt.shape), rec.slot)
-        if self.waiting and (self.waiting[0][0] != key or len(self.waiting) == self.chunk):
-            self.flush()
-        self.waiting.append((key, tgt, ref, gt, rec))
+        super().add((tuple(tgt.shape), tuple(gt.shape), rec.slot), tgt, ref, gt, rec)
 
-    def flush(self):
+    def run_chunk(self, items):
         """One chunk: paste, ONE forward of the clean and the pasted pairs, metrics."""
         from .flownets.utils_model import predict_flow
-        if not self.waiting:
-            return
-        items, self.waiting = self.waiting, []
         K = len(items)
-        f32 = lambda ts: torch.cat([t.detach().to(torch.float32) for t in ts]).contiguous()
-        tgt, ref, gt = f32([it[1] for it in items]), f32([it[2] for it in items]), f32([it[3] for it in items])
+        dev = items[0][1].device
+        tgt, ref, gt = (self.stack_f32([it[i] for it in items], dev) for i in (1, 2, 3))
         recs = [it[4] for it in items]
-        dev = tgt.device
         H, W, Hg, Wg, slot = int(tgt.shape[2]), int(tgt.shape[3]), int(gt.shape[2]), int(gt.shape[3]), recs[0].slot
         stack = lambda name: torch.stack([getattr(r, name) for r in recs]).contiguous()
         p_tgt, m_tgt = stack("patch_tgt"), stack("mask_tgt")
@@ -123,18 +111,15 @@ class _Evaluation:
                                    L.stream()), "eval paste")
         self._mark("paste")
         flows = predict_flow(self.net, None, torch.cat((tgt, adv_tgt)), torch.cat((ref, adv_ref)), self.args)
-        if tuple(flows.shape) != (2 * K, 2, H, W):
-            raise RuntimeError(f"the network returned a flow of shape {tuple(flows.shape)} for {2 * K} pairs of {H}x{W} frames")
-        flows = flows.contiguous()
-        if self.ws is None or self.ws.device != dev:
-            self.ws = torch.zeros(lib.ufr_eval_metrics_workspace_doubles(self.chunk), dtype=torch.float64, device=dev)
+        flows = self.checked_flow(flows, 2 * K, H, W, same_size=True).contiguous()
+        ws = self.workspace(lib.ufr_eval_metrics_workspace_doubles(self.chunk), dev)
         out = torch.zeros(K, 4, dtype=torch.float32, device=dev)
         self._mark("forward")
         L.check(lib.ufr_eval_metrics(L.ptr(flows[:K]), L.ptr(flows[K:]), L.ptr(gt), L.ptr(m_tgt), opt(m_ref), opt(flow), L.ptr(places),
-                                     places_host.ctypes.data, K, H, W, Hg, Wg, slot, slot, self.ignore, L.ptr(self.ws),
-                                     self.ws.numel(), L.ptr(out), 0, K, L.stream()), "eval metrics")
+                                     places_host.ctypes.data, K, H, W, Hg, Wg, slot, slot, self.ignore, L.ptr(ws), ws.numel(),
+                                     L.ptr(out), 0, K, L.stream()), "eval metrics")
         self._mark("metrics")
-        self.results.append(out)
+        return out
 
     def write_back(self):
         """utils_patch.square_transform turns the CALLER's patch and mask in place; the accumulated turns are handed back."""
@@ -162,44 +147,31 @@ def evaluate_patch(flow_net, val_loader, patch, mask, patch_shape, args: Namespa
     from .patch_attack import ERROR_NAMES
     if getattr(args, "true_motion", False):
         _refuse_3d("true_motion")
-    if int(chunk) < 1:
-        raise ValueError("chunk must be positive")
+    ev = _Evaluation(flow_net, patch, mask, patch_shape, args, chunk)         # refuses chunk < 1
     if len(patch.shape) != 4 or tuple(patch.shape[:2]) != (1, 3) or tuple(mask.shape) != tuple(patch.shape):
         raise ValueError("patch and mask must be [1,3,S,S], in patch coordinates")
-    ev = _Evaluation(flow_net, patch, mask, patch_shape, args, chunk)
-    ev.events = getattr(evaluate_patch, "_debug_events", None)
-    frozen = False
+    ev.events = getattr(evaluate_patch, "_debug_events", None)            # tools/bench_patch_eval.py: device events around the entries
     with torch.no_grad():
         for item in val_loader:
             tgt, ref, gt = item[1], item[2], item[3]
             calibrated = len(item) > 5 and len(item[5]) > 0
             if calibrated and not (ev.different or ev.homogeneous):
                 _refuse_3d("an item with calibration (neither different_pos nor HOMOGENUOUS is set)")
-            if tgt.dim() != 4 or tgt.shape[0] != 1 or tgt.shape[1] != 3 or ref.shape != tgt.shape:
-                raise ValueError("the loader yields batch-1 items: tgt and ref [1,3,H,W]")
+            check_pair(tgt, ref, "the loader yields batch-1 items: tgt and ref [1,3,H,W]")
             if gt.dim() != 4 or gt.shape[0] != 1 or gt.shape[1] != 3:
                 raise ValueError("flow_gt must be [1,3,Hg,Wg] (u, v, valid)")
             margin = int(item[4].max()) if calibrated else 0                          # test_patch.py:272-274
             L.require_hip(tgt, "tgt_img", contiguous=False)
             L.require_hip(ref, "ref_img", contiguous=False)
             L.require_hip(gt, "flow_gt", contiguous=False)
-            dev = tgt.device
-            rec = ev.place(tuple(tgt.shape), margin, dev)
-            if not frozen:
-                L.freeze_parameters(flow_net)
-                flow_net.eval()
-                frozen = True
+            rec = ev.place(tuple(tgt.shape), margin, tgt.device)
+            ev.freeze_once(flow_net)
             if ev.homogeneous:                                                        # test_patch.py:255-259
                 tgt, ref, gt = torch.full_like(tgt, 0.5), torch.full_like(ref, 0.5), torch.zeros_like(gt)
-            with torch.cuda.device(dev):
-                ev.add(tgt, ref, gt, rec)
-        if ev.waiting:
-            with torch.cuda.device(ev.waiting[0][1].device):
-                ev.flush()
+            ev.add(tgt, ref, gt, rec)
+        ev.flush()
         ev.write_back()
-        if ev.results:
-            per_item = torch.cat(ev.results).cpu().numpy().astype(np.float64)        # the one host synchronisation of the call
-        else:
-            per_item = np.zeros((0, 4))
+        rows = ev.read()                                                              # the one host synchronisation of the call
+        per_item = rows[0].astype(np.float64) if rows else np.zeros((0, 4))
     mean = per_item.mean(axis=0) if len(per_item) else np.zeros(4)
     return EvalResult(per_item, mean, ev.locations, list(ERROR_NAMES))

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .chunked_eval import StageEvents, freeze
 
 WINDOWED_STAGES = ("restore", "paste", "prefix", "head", "metrics")     # per chunk, in order (tools/bench_patch_sweep.py times them)
 # `cone=None`: the windowed path where it can serve -- 0.366 against 0.755 ms per position for FlowNetC at 384 x 1280
@@ -101,7 +102,7 @@ def _window_size(flow_net, H, W, ph, pw, dev):
     return wh, ww
 
 
-class _Sweep:
+class _Sweep(StageEvents):
     """The buffers and launches of one call."""
 
     def __init__(self, flow_net, tgt, ref, flow_gt, patch_p, mask_p, args, locations, chunk, ignore_mask_flow):
@@ -126,13 +127,6 @@ class _Sweep:
         self.out = torch.zeros(self.rows, 2, dtype=torch.float32, device=self.dev)
         need = L.lib().ufr_sweep_metrics_workspace_doubles(self.K)
         self.ws = torch.zeros(need, dtype=torch.float64, device=self.dev)
-        self.events = None                        # tools/bench_patch_sweep.py: device events around the windowed path's stages
-
-    def _mark(self, stage):
-        if self.events is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.events.append((stage, ev))
 
     def _origin_args(self, c):
         off = c * self.K * 2
@@ -234,8 +228,7 @@ def sweep_patch_locations(flow_net, tgt_img, ref_future_img, flow_gt, patch, mas
     ys, xs, locations = sweep_grid(H, W, ph, pw, int(stride))
     if not locations:
         raise ValueError("no position: the patch fills the frame")
-    L.freeze_parameters(flow_net)
-    flow_net.eval()
+    freeze(flow_net)
     hook = getattr(sweep_patch_locations, "_debug_flows", None)
     events = getattr(sweep_patch_locations, "_debug_events", None)
     with torch.no_grad(), torch.cuda.device(dev):
@@ -247,7 +240,7 @@ def sweep_patch_locations(flow_net, tgt_img, ref_future_img, flow_gt, patch, mas
         windowed = not isinstance(sized, str) and (cone if cone is not None else CONE_BY_DEFAULT)
         sweep = _Sweep(flow_net, f32(tgt_img), f32(ref_future_img), f32(flow_gt), patch_p, mask_p, args, locations, chunk,
                        ignore_mask_flow)
-        sweep.events = events
+        sweep.events = events                                     # tools/bench_patch_sweep.py: the windowed path's stages
         if windowed:
             sweep.run_windowed(*sized, hook)
         else:

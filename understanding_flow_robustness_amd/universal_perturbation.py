@@ -283,6 +283,7 @@ def validation(universal_perturbation, val_loader, model, epoch, args: Namespace
     asymmetric indexing kept: frame 0 takes `[0, 0]`, frame 1 `[:, 1]`), ONE forward of the 2K clean and perturbed pairs, ONE
     ufr_global_metrics (global_eval.py); the host reads once.  Returns `(errors_avg, ["epe", "adv_epe", "cos_sim", "adv_cos_sim"])`.
     `epoch` only labelled the reference's images."""
+    from .chunked_eval import freeze
     from .global_eval import NAMES, Chunks
     error_names = ["epe", "adv_epe", "cos_sim", "adv_cos_sim"]
     if universal_perturbation.dim() != 5 or universal_perturbation.shape[1] != 2:
@@ -290,8 +291,7 @@ def validation(universal_perturbation, val_loader, model, epoch, args: Namespace
     if universal_perturbation.shape[0] != 1:
         raise ValueError("validation takes ONE universal perturbation [1,2,3,H,W]: with more, `[:, 1]` gives the second frame another "
                          "batch size than the first")
-    L.freeze_parameters(model)
-    model.eval()
+    freeze(model)
     ev = Chunks(model, args, chunk, with_noise=False)
     noise = None
     for data in val_loader:
@@ -302,11 +302,7 @@ def validation(universal_perturbation, val_loader, model, epoch, args: Namespace
             noise = (up[0, 0][None].contiguous(), up[:, 1].contiguous())
         if tuple(noise[0].shape) != tuple(tgt_img.shape):
             raise ValueError(f"the universal perturbation is {tuple(noise[0].shape)}, the item is {tuple(tgt_img.shape)}")
-        with torch.cuda.device(tgt_img.device):
-            ev.add(tgt_img, ref_img_future, flow_gt, noise, None)
-    if ev.waiting:
-        with torch.cuda.device(ev.waiting[0][1].device):
-            ev.flush()
+        ev.add(tgt_img, ref_img_future, flow_gt, noise, None)
     per_item, _ = ev.read()
     cols = [NAMES.index(n) for n in ("epe_clean", "epe_adv", "cossim_clean", "cossim_adv")]
     avg = per_item[:, cols].mean(axis=0) if len(per_item) else np.zeros(4)

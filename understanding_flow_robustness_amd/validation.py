@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from .chunked_eval import ChunkedEval, check_pair
 
 COLS = 8             # UFR_VALIDATION_COLS (include/ufr_hip.h)
 MODE_EPE, MODE_COMPONENTS, MODE_CHANNEL0 = 0, 1, 2
@@ -81,86 +82,61 @@ def _rates(epe_all):
 
 
 # ---- fused: chunks of stacked items, one table on the device -------------------------------------------------------------------
-class _Chunks:
-    """Items waiting for their chunk, the chunk's pad, forward and metrics launch, the result rows on the device."""
+class _Chunks(ChunkedEval):
+    """The chunk's pad, forward and metrics launch (chunked_eval.py: the waiting items, the result rows on the device)."""
 
     def __init__(self, model, iters, flowNetC, pad_mode, metric_mode, chunk):
-        if int(chunk) < 1:
-            raise ValueError("chunk must be positive")
+        super().__init__(chunk)
         self.model, self.iters, self.flowNetC = model, iters, bool(flowNetC)
-        self.pad_mode, self.metric_mode, self.chunk = pad_mode, metric_mode, int(chunk)
-        self.waiting, self.rows, self.ws = [], [], None
-        self.events = None               # tools/bench_validation.py: device events around the three stages
-
-    def _mark(self, stage):
-        if self.events is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.events.append((stage, ev))
+        self.pad_mode, self.metric_mode = pad_mode, metric_mode
 
     def add(self, image1, image2, flow_gt, valid):
-        if image1.dim() != 4 or image1.shape[0] != 1 or image1.shape[1] != 3 or image2.shape != image1.shape:
-            raise ValueError("the loader yields batch-1 items: image1 and image2 [1,3,H,W]")
+        check_pair(image1, image2, "the loader yields batch-1 items: image1 and image2 [1,3,H,W]")
         if flow_gt.dim() != 4 or flow_gt.shape[0] != 1 or flow_gt.shape[1] != 2:
             raise ValueError("flow_gt must be [1,2,H,W]")
         if tuple(flow_gt.shape[2:]) != tuple(image1.shape[2:]):
             raise ValueError(f"flow_gt is {tuple(flow_gt.shape[2:])}, the frames are {tuple(image1.shape[2:])}")
         if valid is not None and tuple(valid.shape) != (1,) + tuple(flow_gt.shape[2:]):
             raise ValueError("valid must be [1,H,W]")
-        key = (tuple(image1.shape), tuple(flow_gt.shape), image1.device, valid is None)
-        if self.waiting and (self.waiting[0][0] != key or len(self.waiting) == self.chunk):
-            self.flush()
-        self.waiting.append((key, image1, image2, flow_gt, valid))
+        super().add((tuple(image1.shape), tuple(flow_gt.shape), image1.device, valid is None), image1, image2, flow_gt, valid)
 
-    def flush(self):
-        if not self.waiting:
-            return
-        items, self.waiting = self.waiting, []
+    def run_chunk(self, items):
         K = len(items)
         dev = items[0][1].device
-        f32 = lambda ts: torch.cat([t.detach().to(device=dev, dtype=torch.float32) for t in ts]).contiguous()
-        image1, image2, gt = f32([it[1] for it in items]), f32([it[2] for it in items]), f32([it[3] for it in items])
-        valid = f32([it[4] for it in items]) if items[0][4] is not None else None
+        image1, image2, gt = (self.stack_f32([it[i] for it in items], dev) for i in (1, 2, 3))
+        valid = self.stack_f32([it[4] for it in items], dev) if items[0][4] is not None else None
         H, W = int(image1.shape[2]), int(image1.shape[3])
         left, right, top, bottom = InputPadder(image1.shape, mode=self.pad_mode)._pad if self.pad_mode else (0, 0, 0, 0)
         lib = L.lib()
-        with torch.cuda.device(dev), torch.no_grad():
-            self._mark("start")
-            if self.flowNetC or top or bottom or left or right:
-                pad1, pad2 = (torch.empty(K, 3, H + top + bottom, W + left + right, dtype=torch.float32, device=dev) for _ in range(2))
-                L.check(lib.ufr_validation_pad(L.ptr(image1), L.ptr(image2), L.ptr(pad1), L.ptr(pad2), K, H, W, top, bottom, left, right,
-                                               1 if self.flowNetC else 0, L.stream()), "validation pad")
-            else:
-                pad1, pad2 = image1, image2          # chairs through RAFT: the pad is the identity and nothing is divided
-            self._mark("pad")
-            flow = _forward(self.model, pad1, pad2, self.iters, self.flowNetC)
-            if flow.dim() != 4 or flow.shape[0] != K or flow.shape[1] != 2:
-                raise RuntimeError(f"the network returned a flow of shape {tuple(flow.shape)} for {K} pairs of {H}x{W} frames")
-            flow = flow.to(torch.float32).contiguous()
-            Hp, Wp = int(flow.shape[2]), int(flow.shape[3])
-            self._mark("forward")
-            need = lib.ufr_validation_metrics_workspace_doubles(self.chunk, H, W)
-            if self.ws is None or self.ws.device != dev or self.ws.numel() < need:
-                self.ws = torch.zeros(need, dtype=torch.float64, device=dev)
-            out = torch.zeros(K, COLS, dtype=torch.float64, device=dev)
-            L.check(lib.ufr_validation_metrics(L.ptr(flow), L.ptr(gt), L.ptr(valid) if valid is not None else None, K, Hp, Wp, top, left,
-                                               H, W, self.metric_mode, L.ptr(self.ws), self.ws.numel(), L.ptr(out), 0, K, L.stream()),
-                    "validation metrics")
-            self.rows.append(out)
-            self._mark("metrics")
+        self._mark("start")
+        if self.flowNetC or top or bottom or left or right:
+            pad1, pad2 = (torch.empty(K, 3, H + top + bottom, W + left + right, dtype=torch.float32, device=dev) for _ in range(2))
+            L.check(lib.ufr_validation_pad(L.ptr(image1), L.ptr(image2), L.ptr(pad1), L.ptr(pad2), K, H, W, top, bottom, left, right,
+                                           1 if self.flowNetC else 0, L.stream()), "validation pad")
+        else:
+            pad1, pad2 = image1, image2          # chairs through RAFT: the pad is the identity and nothing is divided
+        self._mark("pad")
+        flow = self.checked_flow(_forward(self.model, pad1, pad2, self.iters, self.flowNetC), K, H, W).to(torch.float32).contiguous()
+        Hp, Wp = int(flow.shape[2]), int(flow.shape[3])
+        self._mark("forward")
+        ws = self.workspace(lib.ufr_validation_metrics_workspace_doubles(self.chunk, H, W), dev)
+        out = torch.zeros(K, COLS, dtype=torch.float64, device=dev)
+        L.check(lib.ufr_validation_metrics(L.ptr(flow), L.ptr(gt), L.ptr(valid) if valid is not None else None, K, Hp, Wp, top, left,
+                                           H, W, self.metric_mode, L.ptr(ws), ws.numel(), L.ptr(out), 0, K, L.stream()),
+                "validation metrics")
+        self._mark("metrics")
+        return out
 
     def read(self):
         """The one host synchronisation: the [N,8] table in loader order."""
-        self.flush()
-        if not self.rows:
-            return np.zeros((0, COLS))
-        return torch.cat(self.rows).cpu().numpy()
+        table = super().read()
+        return table[0] if table else np.zeros((0, COLS))
 
 
 def _fused_table(model, loader, iters, flowNetC, pad_mode, metric_mode, chunk, skip=None):
     model.eval()
     ev = _Chunks(model, iters, flowNetC, pad_mode, metric_mode, chunk)
-    ev.events = getattr(_fused_table, "_debug_events", None)
+    ev.events = getattr(_fused_table, "_debug_events", None)      # tools/bench_validation.py: device events around the stages
     for item in loader:
         image1, image2, flow_gt, valid = item
         for t, name in ((image1, "image1"), (image2, "image2"), (flow_gt, "flow_gt")):

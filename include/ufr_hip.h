@@ -41,7 +41,7 @@ const char* ufr_last_error(void);
 /* Number of HIP devices visible to the library (0 when there is no GPU); never throws. */
 int ufr_device_count(void);
 /* Build manifest: one line "<translation unit> <md5>\n" per object of the library, where md5 is the checksum of the sources the
- * object was COMPILED FROM (csrc/<unit>.hip + csrc/ufr_common.h + include/ufr_hip.h, concatenated in that order).  The Python
+ * object was COMPILED FROM (csrc/<unit>.hip + every header of csrc/ in byte order of their names + include/ufr_hip.h, concatenated in that order).  The Python
  * binding recomputes the checksums from the tree at load and refuses a library holding an object built from other sources (round 5
  * lost two full-suite runs to a library that differed from a clean build of the same tree without anyone being able to say where). */
 const char* ufr_build_manifest(void);
@@ -993,6 +993,47 @@ typedef struct {
 /* -1 when a size is not positive or nscale is outside 1 .. 8 */
 long ufr_train_loss_workspace_doubles(int B, int nscale, const int* h, const int* w);
 int ufr_train_loss(const ufr_train_loss_desc* d, ufr_stream_t stream);
+
+/* RAFT's branch of the same loss (training/utils.py:162-222, the `else` branches) with the convex upsampling that feeds it
+ * (models/raft/raft.py:111-122) folded in: from the npred low-resolution flows and 576-channel masks of the refinement loop to the
+ * loss, the metrics and the gradient of every flow and mask, in three launches whatever npred is (csrc/raft_train_loss.hip).  No
+ * full-resolution prediction and no gradient of one is ever stored.
+ *   up_i   = the convex upsampling of (flow[i], mask[i]): the arithmetic of ufr_convex_upsample_forward, bit for bit;
+ *   g      = gt / div_flow when div_flow > 1 (float32), else gt;
+ *   v      = valid >= 0.5 && (exclude_large ? sqrt(g_u^2 + g_v^2) < max_flow (float32) : true);
+ *   loss   = sum_i weight[i] * sum(v * |up_i - g|) / (B*2*8H*8W)      (the divisor counts every element; `v *` is a product, so
+ *            a NaN in gt makes the loss NaN);
+ *   g_up_i = weight[i] / (B*2*8H*8W) * v * sign(up_i - g), sign(0) = 0: not stored, grad_mask[i] / grad_flow[i] are its images
+ *            under the adjoint of ufr_convex_upsample_backward; every element of both is written, exact zeros where v == 0 and gt
+ *            is finite.
+ * out (device, 8 doubles): loss, then of the LAST prediction over the pixels with v: the float64 sum of the float32 end-point
+ * errors, how many were summed, how many are < 1, < 3, < 5, then 0, 0.
+ * Launch 1: one workgroup per 32 coarse columns of a row holds its gt / valid tile in registers, loops over the predictions, writes
+ * grad_mask and leaves the per-coarse-pixel sums a[k][c] and one row of float64 partials in the workspace; launch 2 gathers every
+ * grad_flow[i] from a; launch 3 (one workgroup) adds the partial rows in ascending order.  No float atomics: two runs are
+ * bit-identical.  ws: ufr_raft_sequence_loss_workspace_doubles() doubles = 18*npred*B*H*W + B*H*ceil(W/32)*(npred + 5).
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: a null descriptor or pointer (the entries of the four tables below
+ * npred included), npred outside 1 .. 32, non-positive sizes, H or B above 65535, a workspace that is too small. */
+#define UFR_RAFT_LOSS_MAX_PREDS 32
+typedef struct {
+  const float* gt;      /* [B,2,8H,8W] */
+  const float* valid;   /* [B,8H,8W]   */
+  int B, H, W;          /* H, W: the 1/8 grid */
+  int npred;            /* 1 .. 32 */
+  const float* flow[UFR_RAFT_LOSS_MAX_PREDS];   /* [B,2,H,W]   = coords1 - coords0 of iteration i */
+  const float* mask[UFR_RAFT_LOSS_MAX_PREDS];   /* [B,576,H,W] */
+  float* grad_flow[UFR_RAFT_LOSS_MAX_PREDS];    /* [B,2,H,W]   */
+  float* grad_mask[UFR_RAFT_LOSS_MAX_PREDS];    /* [B,576,H,W] */
+  double weight[UFR_RAFT_LOSS_MAX_PREDS];       /* gamma ** (npred - i - 1), from the host */
+  double div_flow;         /* > 1: gt / div_flow first */
+  double max_flow;
+  int exclude_large;       /* 0: v = valid >= 0.5 alone (training._valid_mask's `not_excluding`) */
+  double* ws; long ws_elems;
+  double* out;             /* 8 doubles: loss, epe sum, epe count, <1, <3, <5, 0, 0 */
+} ufr_raft_sequence_loss_desc;
+/* -1 when a size is not positive, H or B is above 65535 or npred is outside 1 .. 32 */
+long ufr_raft_sequence_loss_workspace_doubles(int B, int H, int W, int npred);
+int ufr_raft_sequence_loss(const ufr_raft_sequence_loss_desc* d, ufr_stream_t stream);
 
 /* torch.nn.utils.clip_grad_norm_ (error_if_nonfinite=False) + torch.optim.AdamW (amsgrad=False, maximize=False) over many
  * tensors (csrc/optim.hip).  `segs` is a HOST array that is read before the call returns: the segments travel to the kernels BY

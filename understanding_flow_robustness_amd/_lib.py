@@ -116,6 +116,19 @@ class TrainLossDesc(C.Structure):
                 ("ws", C.c_void_p), ("ws_elems", C.c_long), ("out", C.c_void_p)]
 
 
+UFR_RAFT_LOSS_MAX_PREDS = 32
+
+
+class RaftSequenceLossDesc(C.Structure):
+    """ufr_raft_sequence_loss_desc (include/ufr_hip.h), field for field."""
+    _fields_ = [("gt", C.c_void_p), ("valid", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("npred", C.c_int),
+                ("flow", C.c_void_p * UFR_RAFT_LOSS_MAX_PREDS), ("mask", C.c_void_p * UFR_RAFT_LOSS_MAX_PREDS),
+                ("grad_flow", C.c_void_p * UFR_RAFT_LOSS_MAX_PREDS), ("grad_mask", C.c_void_p * UFR_RAFT_LOSS_MAX_PREDS),
+                ("weight", C.c_double * UFR_RAFT_LOSS_MAX_PREDS),
+                ("div_flow", C.c_double), ("max_flow", C.c_double), ("exclude_large", C.c_int),
+                ("ws", C.c_void_p), ("ws_elems", C.c_long), ("out", C.c_void_p)]
+
+
 class AdamwSeg(C.Structure):
     """ufr_adamw_seg (include/ufr_hip.h)."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long)]
@@ -290,6 +303,7 @@ SIGNATURES = {
     "ufr_altcorr_planes_forward": [_vp, _l, C.POINTER(AltCorrPlaneLevels), _vp, _vp, _i, _i, _i, _i, _i, _f, _vp],
     "ufr_conv1_direct": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _l, _i, _vp],
     "ufr_train_loss": [C.POINTER(TrainLossDesc), _vp],
+    "ufr_raft_sequence_loss": [C.POINTER(RaftSequenceLossDesc), _vp],
     "ufr_grad_norm": [C.POINTER(AdamwSeg), _i, _f, _vp, _l, _vp, _vp],
     "ufr_adamw_step": [C.POINTER(AdamwSeg), _i, C.POINTER(AdamwHyper), _vp, _vp],
     "ufr_sweep_paste": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, C.POINTER(ConeChain), _i, _i, _vp, _vp, _vp],
@@ -318,6 +332,7 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_pwc_warp_backward_workspace_bytes": (C.c_long, [_i, _i, _i]),
          "ufr_altcorr_pyramid_workspace_bytes": (C.c_long, [_i, _i, _i, _i, _i, _i]),
          "ufr_train_loss_workspace_doubles": (C.c_long, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+         "ufr_raft_sequence_loss_workspace_doubles": (C.c_long, [_i, _i, _i, _i]),
          "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i]),
          "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i]),
          "ufr_eval_metrics_workspace_doubles": (C.c_long, [_i]),
@@ -357,10 +372,13 @@ _HEADER = os.path.join(os.path.dirname(_HERE), "include", "ufr_hip.h")
 
 
 def source_checksums(csrc: str = _CSRC, header: str = _HEADER) -> dict:
-    """{translation unit: md5 of csrc/<unit>.hip + csrc/ufr_common.h + include/ufr_hip.h}: what csrc/Makefile embeds in each object."""
+    """{translation unit: md5 of csrc/<unit>.hip + every csrc/*.h (byte order of the names) + include/ufr_hip.h}: what csrc/Makefile
+    embeds in each object."""
     import hashlib
-    with open(os.path.join(csrc, "ufr_common.h"), "rb") as f:
-        shared = f.read()
+    shared = b""
+    for name in sorted(n.encode() for n in os.listdir(csrc) if n.endswith(".h")):
+        with open(os.path.join(csrc, name.decode()), "rb") as f:
+            shared += f.read()
     with open(header, "rb") as f:
         shared += f.read()
     sums = {}

@@ -41,7 +41,7 @@ std::map<std::string, std::string>& tu_table() {      // function-local: constru
 void register_tu(const char* name, const char* sum) { tu_table()[name] = sum; }
 }  // namespace ufr
 
-// "<translation unit> <md5 of its .hip + ufr_common.h + include/ufr_hip.h at compile time>\n" per object, sorted by name
+// "<translation unit> <md5 of its .hip + the headers of this directory + include/ufr_hip.h at compile time>\n" per object, sorted by name
 extern "C" const char* ufr_build_manifest(void) {
   static std::string text;
   static std::once_flag once;

@@ -8,33 +8,15 @@
 // Backward: kernel A recomputes the softmax, writes d loss/d mask and reduces, per coarse pixel, the 64
 // sub-pixel terms of  a[k][c] = sum_ij softmax_k * g_up[c]  in registers + LDS (fixed order, no atomics);
 // kernel B gathers d loss/d flow[n,c,h',w'] = 8 * sum_k a[k][c] at (h'-ky+1, w'-kx+1).
-#include "ufr_common.h"
+#include "convex_upsample_dev.h"
 
 namespace {
 
 constexpr int CU_W = 32;          // coarse columns per workgroup
 constexpr int CU_NT = 256;        // 8 sub-pixels x 32 columns per pass, 8 passes
 
-__device__ __forceinline__ void softmax9(const float* __restrict__ m, size_t stride, float* s) {
-  float mx = m[0];
-#pragma unroll
-  for (int k = 1; k < 9; ++k) mx = fmaxf(mx, m[k * stride]);
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { s[k] = expf(m[k * stride] - mx); sum += s[k]; }
-  const float inv = 1.0f / sum;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) s[k] *= inv;
-}
-
-// 8 * flow at the 3x3 neighbours (zero padding, like F.unfold(padding=1))
-__device__ __forceinline__ void neighbours(const float* __restrict__ flow_nc, int h, int w, int H, int W, float* f) {
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int hh = h + k / 3 - 1, ww = w + k % 3 - 1;
-    f[k] = (hh >= 0 && hh < H && ww >= 0 && ww < W) ? 8.0f * flow_nc[hh * W + ww] : 0.f;
-  }
-}
+using ufr::dev::softmax9;         // shared with raft_train_loss.hip (convex_upsample_dev.h)
+using ufr::dev::neighbours;
 
 __global__ __launch_bounds__(CU_NT) void convex_up_fwd(const float* __restrict__ flow, const float* __restrict__ mask,
                                                        float* __restrict__ up, int H, int W) {

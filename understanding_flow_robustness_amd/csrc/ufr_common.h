@@ -23,7 +23,7 @@ inline hipStream_t as_stream(ufr_stream_t s) { return reinterpret_cast<hipStream
 hipError_t ensure_dynamic_lds(const void* fn, size_t bytes);
 
 // Build manifest (capi.hip, `ufr_build_manifest()`): every translation unit registers, at load, the checksum of the sources it was
-// COMPILED FROM (its .hip + this header + include/ufr_hip.h; the Makefile passes it as -DUFR_TU_SUM).  _lib.py recomputes the
+// COMPILED FROM (its .hip + every header of this directory + include/ufr_hip.h; the Makefile passes it as -DUFR_TU_SUM).  _lib.py recomputes the
 // checksums from the tree and refuses a library that holds an object built from other sources.
 void register_tu(const char* name, const char* sum);
 struct TuRegistrar {

@@ -317,6 +317,25 @@ def coords_grid(batch, ht, wd, device):
     return torch.stack((xs, ys), dim=0).float()[None].repeat(batch, 1, 1, 1)
 
 
+class RaftPredictions:
+    """What `RAFT.forward(lowres_predictions=True)` returns in training mode: per iteration the low-resolution flow
+    (`coords1 - coords0`, [N,2,H,W]) and the upsampling mask ([N,576,H,W]), both graph tensors.  `training.sequence_loss` and
+    `training.multiscale_epe` take it in place of the list and run upsampling, loss and gradients as one pass (csrc/raft_train_loss.hip);
+    `upsampled()` is the reference's list."""
+
+    def __init__(self, flows, masks):
+        self.flows, self.masks = list(flows), list(masks)
+        if len(self.flows) != len(self.masks):
+            raise ValueError(f"RaftPredictions: {len(self.flows)} flows and {len(self.masks)} masks")
+
+    def __len__(self):
+        return len(self.flows)
+
+    def upsampled(self):
+        """`RAFT.upsample_flow` of every pair, autograd intact: what the default forward returns."""
+        return [RAFT.upsample_flow(f, m) for f, m in zip(self.flows, self.masks)]
+
+
 class RAFT(nn.Module):
     def __init__(self, args, return_feat_maps: bool = False):
         super().__init__()
@@ -378,7 +397,9 @@ class RAFT(nn.Module):
         up = torch.sum(mask * up, dim=2).permute(0, 1, 4, 2, 5, 3)
         return up.reshape(N, 2, 8 * H, 8 * W)
 
-    def forward(self, image1, image2, iters=12, flow_init=None, test_mode=False):
+    def forward(self, image1, image2, iters=12, flow_init=None, test_mode=False, lowres_predictions=False):
+        """`lowres_predictions` (training mode only, ignored with `test_mode`): the iterations are not upsampled; a RaftPredictions
+        with every iteration's low-resolution flow and mask is returned in place of the list (training.sequence_loss takes it)."""
         iters = self.args.iters                                        # raft.py:126 (argument ignored)
         from ..raft_glue import normalize_pair
         stack = normalize_pair(image1, image2)                         # both frames in one pass, as the stack the feature encoder takes
@@ -391,7 +412,7 @@ class RAFT(nn.Module):
         prec = _ig.products(self.products())      # the engines built / looked up inside take this many products (6 = float32-accurate)
 
         if not hasattr(self, "cnet"):
-            return self._forward_wo_context(image1, image2, stack, prec, flow_init, test_mode)
+            return self._forward_wo_context(image1, image2, stack, prec, flow_init, test_mode, lowres_predictions)
 
         def context():
             with prec:
@@ -422,7 +443,7 @@ class RAFT(nn.Module):
         else:
             net, inp = context()
 
-        return self._refine(image1, net, inp, corr_fn, prec, flow_init, test_mode)
+        return self._refine(image1, net, inp, corr_fn, prec, flow_init, test_mode, lowres_predictions)
 
     def _context_stem(self, x, n):
         """FlowNetC's stem of both frames and conv_redir as ONE schedule on the igemm (plane_graph.stem_graph with `head`), forward and
@@ -458,7 +479,7 @@ class RAFT(nn.Module):
             halves = torch.tanh(net), torch.relu(inp)
         return fmap1, fmap2, halves[0], halves[1]
 
-    def _forward_wo_context(self, image1, image2, stack, prec, flow_init, test_mode):
+    def _forward_wo_context(self, image1, image2, stack, prec, flow_init, test_mode, lowres_predictions=False):
         with prec:
             fmap1, fmap2, net, inp = self.context_features(image1, image2, stack)
         fmap1, fmap2 = fmap1.float().contiguous(), fmap2.float().contiguous()
@@ -466,10 +487,12 @@ class RAFT(nn.Module):
             corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, share_grad=True)
         else:
             corr_fn = CorrBlock(fmap1, fmap2, num_levels=self.args.corr_levels, radius=self.args.corr_radius)
-        return self._refine(image1, net, inp, corr_fn, prec, flow_init, test_mode)
+        return self._refine(image1, net, inp, corr_fn, prec, flow_init, test_mode, lowres_predictions)
 
-    def _refine(self, image1, net, inp, corr_fn, prec, flow_init, test_mode):
+    def _refine(self, image1, net, inp, corr_fn, prec, flow_init, test_mode, lowres_predictions=False):
         """raft.py:181-233: the iterations and the convex upsampling."""
+        lowres = bool(lowres_predictions) and not test_mode
+        flows, masks = [], []
         iters = self.args.iters
         N, _, H, W = image1.shape
         if test_mode and flow_init is None and self._engine_ok(net, H, W):
@@ -491,9 +514,14 @@ class RAFT(nn.Module):
             net, up_mask, delta_flow = self.update_block(net, inp, corr, coords1 - coords0, want_mask=want,
                                                          cache=gru_cache)
             coords1 = coords1 + delta_flow
-            if want:
+            if lowres:
+                flows.append(coords1 - coords0)
+                masks.append(up_mask)
+            elif want:
                 flow_up = self.upsample_flow(coords1 - coords0, up_mask)
                 flow_predictions.append(flow_up)
         if test_mode:
             return coords1 - coords0, flow_up
+        if lowres:
+            return RaftPredictions(flows, masks)
         return flow_predictions

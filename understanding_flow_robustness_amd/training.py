@@ -3,8 +3,10 @@ its inner training iteration (training/utils.py:68-239, training/train.py:225-28
 
   sequence_loss, multiscale_epe   value and gradient of every prediction in ONE pass over all scales (csrc/train_loss.hip) for HIP
                                   float32 tensors of the `flowNetC or pwc` branch whose ground-truth sides are integer multiples of
-                                  every prediction's; everything else (CPU, float64, other ratios, the RAFT branch) runs the
-                                  plain-torch restatement below, which is also the yardstick of the GPU tests.
+                                  every prediction's; everything else (CPU, float64, other ratios, the RAFT branch on a list)
+                                  runs the plain-torch restatement below, which is also the yardstick of the GPU tests.  RAFT's
+                                  branch on a `flownets.raft.RaftPredictions` (the low-resolution flows and masks): convex
+                                  upsampling, loss and every gradient in ONE pass (csrc/raft_train_loss.hip).
   ClippedAdamW                    torch.optim.AdamW whose step() is a fused multi-tensor kernel with the gradient clipping of
                                   `clip_grad_norm_` folded in (csrc/optim.hip); state and param_groups are torch's own.
   fetch_optimizer                 that optimiser + torch's OneCycleLR, as the reference configures them.
@@ -160,10 +162,88 @@ def _loss_kernel(kind, flow_preds, flow_gt, weights, div_flow):
     return loss, metrics
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the losses: RAFT's branch from the low-resolution predictions (flownets.raft.RaftPredictions), convex upsampling included
+def _is_raft_predictions(flow_preds) -> bool:
+    from .flownets.raft import RaftPredictions
+    return isinstance(flow_preds, RaftPredictions)
+
+
+def _raft_kernel_serves(preds, flow_gt, valid) -> bool:
+    """Everything HIP float32 and contiguous on one device, gt [B,2,8H,8W], valid [B,8H,8W], 1 .. 32 pairs of [B,2,H,W] / [B,576,H,W]."""
+    def dense(t, shape):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == flow_gt.device and t.dtype == torch.float32
+                and tuple(t.shape) == shape and t.is_contiguous())
+    n = len(preds)
+    if not (1 <= n <= L.UFR_RAFT_LOSS_MAX_PREDS and isinstance(flow_gt, torch.Tensor) and flow_gt.dim() == 4
+            and isinstance(preds.flows[0], torch.Tensor) and preds.flows[0].dim() == 4):
+        return False
+    B, _, H, W = preds.flows[0].shape
+    if not (B > 0 and H > 0 and W > 0 and dense(flow_gt, (B, 2, 8 * H, 8 * W)) and dense(valid, (B, 8 * H, 8 * W))):
+        return False
+    return all(dense(f, (B, 2, H, W)) and dense(m, (B, 576, H, W)) for f, m in zip(preds.flows, preds.masks))
+
+
+class _RaftTrainLoss(torch.autograd.Function):
+    """Forward computes the value, the metric sums and the gradient of every flow and mask (csrc/raft_train_loss.hip); backward scales
+    the gradients, in place: they are the size of the masks, and like autograd's saved tensors they are gone after one backward."""
+
+    @staticmethod
+    def forward(ctx, flow_gt, valid, weights, div_flow, max_flow, exclude_large, *tensors):
+        lib = L.lib()
+        n = len(tensors) // 2
+        flows, masks = tensors[:n], tensors[n:]
+        B, _, H, W = flows[0].shape
+        grads = [torch.empty_like(t) for t in tensors]
+        d = L.RaftSequenceLossDesc()
+        d.gt, d.valid, d.B, d.H, d.W, d.npred = flow_gt.data_ptr(), valid.data_ptr(), B, H, W, n
+        for i in range(n):
+            d.flow[i], d.mask[i], d.grad_flow[i], d.grad_mask[i] = (flows[i].data_ptr(), masks[i].data_ptr(), grads[i].data_ptr(),
+                                                                    grads[n + i].data_ptr())
+            d.weight[i] = float(weights[i])
+        d.div_flow, d.max_flow, d.exclude_large = float(div_flow), float(max_flow), int(bool(exclude_large))
+        need = lib.ufr_raft_sequence_loss_workspace_doubles(B, H, W, n)
+        ws = torch.empty(need, dtype=torch.float64, device=flow_gt.device)
+        out = torch.empty(8, dtype=torch.float64, device=flow_gt.device)
+        d.ws, d.ws_elems, d.out = ws.data_ptr(), need, out.data_ptr()
+        with torch.cuda.device(flow_gt.device):
+            L.check(lib.ufr_raft_sequence_loss(C.byref(d), L.stream()), "ufr_raft_sequence_loss")
+        ctx.grads = grads
+        ctx.mark_non_differentiable(out)
+        return out[0].to(torch.float32), out
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_out):
+        grads, ctx.grads = ctx.grads, None
+        if grads is None:
+            raise RuntimeError("the fused RAFT loss keeps its gradients for one backward only (they are scaled in place)")
+        torch._foreach_mul_(grads, grad_loss)
+        return (None, None, None, None, None, None) + tuple(grads)
+
+
+def _raft_loss_kernel(kind, preds, flow_gt, valid, gamma, max_flow, not_excluding, div_flow):
+    n = len(preds)
+    weights = [_scale_weight(i, n, gamma, True, False) for i in range(n)]
+    loss, out = _RaftTrainLoss.apply(flow_gt, valid, weights, div_flow, max_flow, not not_excluding, *preds.flows, *preds.masks)
+    value, epe_sum, epe_n, n1, n3, n5, _, _ = out.cpu().tolist()                  # the one device-to-host copy of the call
+    nan = float("nan")
+    metrics = {"epe": epe_sum / epe_n if epe_n else nan, "1px": n1 / epe_n if epe_n else nan, "3px": n3 / epe_n if epe_n else nan,
+               "5px": n5 / epe_n if epe_n else nan}
+    if kind == 1:
+        metrics["loss"] = value
+    loss._ufr_host_value = value            # finetune_step's NaN test reads this instead of asking the device again
+    return loss, metrics
+
+
 def sequence_loss(flow_preds, flow_gt, valid, gamma=0.8, max_flow=MAX_FLOW, flowNetC=False, pwc=False, not_excluding=False,
                   div_flow=1, flownetc_weighing=False):
     """The reference's `sequence_loss` (training/utils.py:148-222): (loss, metrics).  With `flowNetC or pwc`: per scale the L1
-    distance to the area-interpolated, rescaled ground truth, averaged over the elements that are not NaN."""
+    distance to the area-interpolated, rescaled ground truth, averaged over the elements that are not NaN.  A RaftPredictions in
+    place of the list: RAFT's branch with the upsampling folded in, where `_raft_kernel_serves`; its `upsampled()` list elsewhere."""
+    if _is_raft_predictions(flow_preds):
+        if not (flowNetC or pwc) and _raft_kernel_serves(flow_preds, flow_gt, valid):
+            return _raft_loss_kernel(0, flow_preds, flow_gt, valid, gamma, max_flow, not_excluding, div_flow)
+        flow_preds = flow_preds.upsampled()
     flow_preds = list(flow_preds)
     if (flowNetC or pwc) and _kernel_serves(flow_preds, flow_gt):
         n = len(flow_preds)
@@ -176,7 +256,11 @@ def multiscale_epe(flow_preds, flow_gt, valid, gamma=0.8, max_flow=MAX_FLOW, flo
                    flownetc_weighing=False, pwc=False):
     """The reference's `multiscale_epe` (training/utils.py:68-145): (loss, metrics).  With `flowNetC or pwc`: per scale the
     end-point error (+ 1e-5 under the root) to the area-interpolated, rescaled ground truth, averaged over the pixels that are not
-    NaN; a scale without such a pixel is skipped."""
+    NaN; a scale without such a pixel is skipped.  A RaftPredictions in place of the list: as in `sequence_loss`."""
+    if _is_raft_predictions(flow_preds):
+        if not (flowNetC or pwc) and _raft_kernel_serves(flow_preds, flow_gt, valid):
+            return _raft_loss_kernel(1, flow_preds, flow_gt, valid, gamma, max_flow, not_excluding, div_flow)
+        flow_preds = flow_preds.upsampled()
     flow_preds = list(flow_preds)
     if (flowNetC or pwc) and _kernel_serves(flow_preds, flow_gt):
         n = len(flow_preds)
@@ -293,25 +377,33 @@ def _flag(args, name, default=False):
     return getattr(args, name, default)
 
 
-def finetune_step(model, optimizer, scheduler, image1, image2, flow, valid, args):
+def _fused_raft(model, image1, image2) -> bool:
+    from .flownets.raft import RAFT
+    return isinstance(model, RAFT) and all(t.is_cuda and t.dtype == torch.float32 for t in (image1, image2))
+
+
+def finetune_step(model, optimizer, scheduler, image1, image2, flow, valid, args, fused_raft_loss=True):
     """One inner training iteration of the reference (training/train.py:225-282) without its GradScaler: zero_grad, forward,
     loss, backward, clipped AdamW step, scheduler step; (loss, metrics).  A NaN loss returns before the backward, as there.
     `band_conv.native_training()` is the caller's choice: inside it the FlowNetC family and PWC-Net run their convolutions on the
     hand-written kernels, outside it (and for RAFT) on torch operators; the loss and the optimiser are the ones above either way.
-    `optimizer` is a ClippedAdamW (`fetch_optimizer`); any other torch optimiser gets `clip_grad_norm_` and its own step()."""
+    `optimizer` is a ClippedAdamW (`fetch_optimizer`); any other torch optimiser gets `clip_grad_norm_` and its own step().
+    `fused_raft_loss`: this package's RAFT on HIP float32 frames hands the loss its low-resolution predictions, and upsampling,
+    loss and their gradients run as one pass (csrc/raft_train_loss.hip); False: the list of upsampled predictions, as before."""
     flownetc = bool(_flag(args, "flowNetC") or _flag(args, "flowNetCFlexible"))
     pwc = bool(_flag(args, "pwc"))
     optimizer.zero_grad()
+    raft_kw = {"lowres_predictions": True} if fused_raft_loss and not (flownetc or pwc) and _fused_raft(model, image1, image2) else {}
     if _flag(args, "adv_train") or _flag(args, "finetune"):
         if flownetc or pwc:
             flow_predictions = model(image1, image2)
         else:                                                       # RAFT
-            flow_predictions = model(image1 * 255.0, image2 * 255.0, iters=_flag(args, "iters", 12))
+            flow_predictions = model(image1 * 255.0, image2 * 255.0, iters=_flag(args, "iters", 12), **raft_kw)
     else:
         if flownetc:
             flow_predictions = model(image1 / 255.0, image2 / 255.0)
         else:                                                       # RAFT (and, as in the reference, PWC-Net)
-            flow_predictions = model(image1, image2) if pwc else model(image1, image2, iters=_flag(args, "iters", 12))
+            flow_predictions = model(image1, image2) if pwc else model(image1, image2, iters=_flag(args, "iters", 12), **raft_kw)
     loss_fn = multiscale_epe if _flag(args, "multiscaleEPE") else sequence_loss
     loss, metrics = loss_fn(flow_predictions, flow, valid, _flag(args, "gamma", 0.8), flowNetC=flownetc,
                             not_excluding=_flag(args, "no_excluding"), div_flow=_flag(args, "div_flow", 1),

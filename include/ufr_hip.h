@@ -1211,6 +1211,37 @@ long ufr_validation_metrics_workspace_doubles(int K, int H, int W);   /* -1 when
 int ufr_validation_metrics(const float* pred, const float* gt, const float* valid, int K, int Hp, int Wp, int top, int left, int H,
                            int W, int mode, double* ws, long ws_elems, double* out, int row0, int rows, ufr_stream_t stream);
 
+/* ---- test-server submissions (csrc/submission.hip) ------------------------------------------------------------------------------
+ * training/evaluate.py:201-267 (`create_sintel_submission`, `create_kitti_submission`) writes one flow file per item; the Sintel
+ * loop may warm-start every forward with `forward_interpolate` (models/raft/utils/utils.py:33-59) of the previous frame's
+ * low-resolution flow: a D2H copy, scipy's `griddata(method="nearest")` over the forward-splatted points, an H2D copy.
+ *
+ * ufr_forward_interpolate: flow [B,2,H,W] -> out [B,2,H,W], every item on its own.  Source point i (row-major, x0 = i % W,
+ *   y0 = i / W) carries (dx, dy) = flow[b,:,y0,x0] and lies at x1 = (double)x0 + (double)dx, y1 = (double)y0 + (double)dy (numpy adds
+ *   an int64 grid to a float32 flow: float64).  It is VALID iff x1 > 0 && x1 < W && y1 > 0 && y1 < H (strict; a NaN makes it invalid).
+ *   out[b,:,gy,gx] = the (dx, dy) -- copied bit for bit -- of the valid point with the smallest (x1 - gx)^2 + (y1 - gy)^2, each
+ *   operation rounded on its own in float64.  Two valid points at exactly equal distance: the lowest index wins (the reference's
+ *   choice there is its KD-tree's and unspecified).  An item without a valid point: every output of it is NaN (scipy 1.15's answer).
+ *   The search is exact -- brute force over all points, staged through LDS -- with no atomics, no allocation and no synchronisation:
+ *   one launch of ceil(H * W * slices / 256) x B workgroups, where `slices` neighbouring lanes share a target pixel, split the points
+ *   among them and combine their (distance, index) minima lexicographically, which gives the same bits for every `slices`.
+ *   ufr_forward_interpolate is the entry to call; it runs the measured default (UFR_FORWARD_INTERPOLATE_SLICES,
+ *   profiles/submission.json).  ufr_forward_interpolate_sliced, slices in {1, 4, 16}, is a MEASUREMENT entry: it exists so that
+ *   tools/bench_submission.py and the tests can run every lane count; the result does not depend on `slices`, and callers should
+ *   not build on the parameter.  Any W; no alignment is required.
+ * ufr_flow_encode: pred [K,2,Hp,Wp] (the prediction on the PADDED frame, read at (y + top, x + left) as in ufr_validation_metrics)
+ *   -> mode 0: float32 [K,H,W,2], u and v interleaved: the payload of a `.flo` file (data_utils.writeFlow);
+ *      mode 1: uint16 [K,H,W,3] = (trunc(64 * u + 32768), trunc(64 * v + 32768), 1): data_utils.writeFlowKITTI.  float32 arithmetic
+ *              (64 * x is exact, one rounding in the sum), truncation towards zero.  DEFINED DEVIATION: numpy's cast of a value outside
+ *              the target range is undefined; here a value below 0 or NaN gives 0 and a value at or above 65536 gives 65535.
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: null pointers, B / K < 1, B > 65535 (the items are the grid's second
+ *   axis), non-positive sizes, H * W (Hp * Wp) of 2^29 or more, slices outside {1, 4, 16}; for the encoder also negative pads, a crop that leaves the padded frame and a mode outside 0..1. */
+#define UFR_FORWARD_INTERPOLATE_SLICES 16
+int ufr_forward_interpolate(const float* flow, float* out, int B, int H, int W, ufr_stream_t stream);
+int ufr_forward_interpolate_sliced(const float* flow, float* out, int B, int H, int W, int slices, ufr_stream_t stream);
+int ufr_flow_encode(const float* pred, void* out, int K, int Hp, int Wp, int top, int left, int H, int W, int mode,
+                    ufr_stream_t stream);
+
 /* ---- feature-map statistics (csrc/feature_stats.hip) -------------------------------------------------------------------------
  * patch_attacks/test_patch_embeddings.py takes np.mean over the pixels of every feature map of a forward; here the maps stay where
  * the engine left them and only their per-image, per-channel SUMS leave the device, all segments of a forward in one result matrix.

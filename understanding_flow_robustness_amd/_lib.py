@@ -314,6 +314,9 @@ SIGNATURES = {
     "ufr_global_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
     "ufr_validation_pad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ufr_validation_metrics": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
+    "ufr_forward_interpolate": [_vp, _vp, _i, _i, _i, _vp],
+    "ufr_forward_interpolate_sliced": [_vp, _vp, _i, _i, _i, _i, _vp],
+    "ufr_flow_encode": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ufr_feature_stats": [C.POINTER(FeatureStatsSeg), _i, _vp, _l, _vp, _i, _l, _l, _vp],
     "ufr_abs_sums": [_vp, _vp, _l, _vp, _l, _vp, _vp],
     "ufr_momentum_update": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _vp],

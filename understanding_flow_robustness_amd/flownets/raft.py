@@ -380,6 +380,13 @@ class RAFT(nn.Module):
             extra = "not the raft-things update block (corr_levels 4, corr_radius 4, motion downsampling)"
         return L.engine_gate(self, net, 8, 8, extra=extra if os.environ.get("UFR_ENGINE", "1") == "1" and net.is_cuda else None)
 
+    @staticmethod
+    def flow_init_served(flow_init, net, H, W) -> bool:
+        """A warm start the refinement engine takes: none, or a HIP float32 [N,2,H/8,W/8] on the context features' device."""
+        return flow_init is None or (torch.is_tensor(flow_init) and flow_init.is_cuda and flow_init.device == net.device
+                                     and flow_init.dtype == torch.float32
+                                     and tuple(flow_init.shape) == (net.shape[0], 2, H // 8, W // 8))
+
     def freeze_bn(self):
         for m in self.modules():
             if isinstance(m, nn.BatchNorm2d):
@@ -495,11 +502,12 @@ class RAFT(nn.Module):
         flows, masks = [], []
         iters = self.args.iters
         N, _, H, W = image1.shape
-        if test_mode and flow_init is None and self._engine_ok(net, H, W):
-            # the 12 iterations as one explicit schedule on the native engine (raft_engine.py): same operands, same result
+        if test_mode and self.flow_init_served(flow_init, net, H, W) and self._engine_ok(net, H, W):
+            # the 12 iterations as one explicit schedule on the native engine (raft_engine.py): same operands, same result; a warm
+            # start of another device, dtype or shape takes the torch spelling below
             from ..raft_engine import refine
             with prec:
-                flow_lr, up_mask = refine(self, net.contiguous(), inp.contiguous(), corr_fn, H, W)
+                flow_lr, up_mask = refine(self, net.contiguous(), inp.contiguous(), corr_fn, H, W, flow_init)
             return flow_lr, self.upsample_flow(flow_lr, up_mask)
         coords0 = coords_grid(N, H // 8, W // 8, image1.device)
         coords1 = coords0.clone()

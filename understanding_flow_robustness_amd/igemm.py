@@ -58,7 +58,8 @@ class Planes:
         """planes[chunk0 + k/32][m][k%32] = split(scale * src[m][k]) for a row-major float32 matrix src [M, K] (the operand of a
         GEMM reduced over the matrix's columns; rows = this buffer's pixels)."""
         L.require_hip(src, "src", contiguous=False)
-        if src.dim() != 2 or src.stride(1) != 1 or src.dtype != torch.float32 or src.shape[0] != self.M or chunk0 + pad32(src.shape[1]) // 32 > self.chunks:
+        # (a single column has no column stride to speak of: torch keeps whatever stride the view had, e.g. after `.t().contiguous()`)
+        if src.dim() != 2 or (src.stride(1) != 1 and src.shape[1] != 1) or src.dtype != torch.float32 or src.shape[0] != self.M or chunk0 + pad32(src.shape[1]) // 32 > self.chunks:
             raise RuntimeError("Planes.load_rowmajor: shape mismatch")
         L.check(L.lib().ufr_rowmajor_to_planes(L.ptr(src), src.stride(0), src.shape[0], src.shape[1], float(scale), L.ptr(self.t),
                                                self.plane_stride, int(chunk0), self.M, L.stream()), "row-major -> planes")

@@ -120,6 +120,59 @@ def flow_write_png(fpath, u, v, valid=None):
     png_write(str(fpath), np.dstack((u_, v_, valid_)))
 
 
+_FLO_TAG = b"PIEH"          # the float32 202021.25 of the Middlebury format
+
+
+def write_flo(path, flow_hw2):
+    """dataset_utils/data_utils.py:228-256 (`writeFlow`), byte for byte: the tag, int32 width, int32 height, then float32 rows
+    with u and v interleaved.  `flow_hw2` is [H,W,2]."""
+    flow = np.asarray(flow_hw2)
+    if flow.ndim != 3 or flow.shape[2] != 2:
+        raise ValueError(f"write_flo takes a flow of shape [H,W,2], not {flow.shape}")
+    height, width = flow.shape[:2]
+    with open(path, "wb") as f:
+        f.write(_FLO_TAG + struct.pack("<ii", width, height))
+        f.write(np.ascontiguousarray(flow, dtype="<f4").tobytes())
+
+
+def read_flo(path):
+    """The inverse of `write_flo`: float32 [H,W,2]."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:4] != _FLO_TAG:
+        raise ValueError(f"{path}: not a .flo file")
+    width, height = struct.unpack("<ii", raw[4:12])
+    if width < 1 or height < 1 or len(raw) != 12 + 8 * width * height:
+        raise ValueError(f"{path}: {len(raw)} bytes for a flow of {height} x {width}")
+    return np.frombuffer(raw, dtype="<f4", offset=12).reshape(height, width, 2).astype(np.float32)
+
+
+def flow_kitti_codes(uv):
+    """float [H,W,2] -> uint16 [H,W,3], the array dataset_utils/data_utils.py:274-277 (`writeFlowKITTI`) builds: 64 * uv + 2^15 in
+    the flow's own precision, a channel of ones, a truncating cast.  numpy leaves the cast of a value outside 0..65535 undefined;
+    here (and in ufr_flow_encode, mode 1) a value below 0 or NaN gives 0 and a value at or above 65536 gives 65535."""
+    uv = np.asarray(uv)
+    if uv.ndim != 3 or uv.shape[2] != 2:
+        raise ValueError(f"a flow of shape [H,W,2] is needed, not {uv.shape}")
+    v = 64.0 * uv + 2 ** 15
+    with np.errstate(invalid="ignore"):
+        v = np.where(v >= 0, np.minimum(v, 65535), 0)
+    return np.concatenate([v, np.ones(v.shape[:2] + (1,), v.dtype)], axis=-1).astype(np.uint16)
+
+
+def write_flow_kitti(path, uv_or_encoded):
+    """`writeFlowKITTI` through `png_write`: a float flow [H,W,2] (encoded by `flow_kitti_codes`) or the uint16 [H,W,3] codes
+    themselves (ufr_flow_encode, mode 1) -> a 16-bit RGB PNG with R = u, G = v, B = 1.  The PIXEL VALUES are the reference's (it
+    hands cv2.imwrite the reversed, BGR, array); the compressed bytes are not: the reference writes with cv2, which is not a
+    dependency here, and a PNG's bytes depend on the encoder's filter and deflate choices."""
+    arr = np.asarray(uv_or_encoded)
+    if arr.dtype != np.uint16:
+        arr = flow_kitti_codes(arr)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError(f"encoded KITTI flow must be uint16 [H,W,3], not {arr.shape}")
+    png_write(str(path), arr)
+
+
 def save_patch(patch, path):
     """patch_attacks/main.py:339: `torch.save(patch, ...)` with `patch` the numpy array [1,3,S,S]."""
     if torch.is_tensor(patch):

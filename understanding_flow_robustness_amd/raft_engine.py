@@ -445,7 +445,7 @@ class _RaftRefine(torch.autograd.Function):
     """The refinement loop as one Function of (net0, inp, lookup operands); static buffers: see flownetc_engine._EngineHead."""
 
     @staticmethod
-    def forward(ctx, net0, inp, engine, alt, scale, f1, *rest):
+    def forward(ctx, net0, inp, engine, alt, scale, flow_init, f1, *rest):
         if alt:
             src = dict(alt=True, f1=f1, f2=list(rest), scale=float(scale))
             from .flownets.raft_corr import AltCorrPlanes
@@ -453,7 +453,7 @@ class _RaftRefine(torch.autograd.Function):
                 src["planes"] = AltCorrPlanes(f1, list(rest))
         else:
             src = dict(alt=False, vols=list(rest))
-        flow_lr, up_mask = engine.forward(net0, inp, src)
+        flow_lr, up_mask = engine.forward(net0, inp, src, flow_init)   # (flow_init: the loop detaches coords1 first, raft.py:190)
         ctx.engine, ctx.src, ctx.generation = engine, src, engine.generation
         return flow_lr.clone(), up_mask.clone()
 
@@ -477,10 +477,10 @@ class _RaftRefine(torch.autograd.Function):
         if src["alt"] and src.get("dense"):
             g_f1, g_f2 = alt_dense_adjoint(src["f1"], src["f2"], src["g_vols"], src["scale"])
             src["g_vols"] = None                                       # (313 MB per pair: released with this backward)
-            return (g_net0.clone(), g_inp.clone(), None, None, None, g_f1, *g_f2)
+            return (g_net0.clone(), g_inp.clone(), None, None, None, None, g_f1, *g_f2)
         if src["alt"]:
-            return (g_net0.clone(), g_inp.clone(), None, None, None, src["g_f1"], *src["g_f2"])
-        return (g_net0.clone(), g_inp.clone(), None, None, None, None, *src["g_vols"])
+            return (g_net0.clone(), g_inp.clone(), None, None, None, None, src["g_f1"], *src["g_f2"])
+        return (g_net0.clone(), g_inp.clone(), None, None, None, None, None, *src["g_vols"])
 
 
 def get_engine(net, B: int, H: int, W: int, device) -> RaftUpdateEngine:
@@ -496,12 +496,15 @@ def get_engine(net, B: int, H: int, W: int, device) -> RaftUpdateEngine:
     return eng
 
 
-def refine(net, net0, inp, corr_fn, H: int, W: int):
+def refine(net, net0, inp, corr_fn, H: int, W: int, flow_init=None):
     """(flow at 1/8 resolution, up_mask) of the 12 iterations on the engine; corr_fn = the AlternateCorrBlock / CorrBlock the
-    reference's loop would call (its operands are taken, its per-iteration autograd Functions are not used)."""
+    reference's loop would call (its operands are taken, its per-iteration autograd Functions are not used).  `flow_init`
+    (`RAFT.flow_init_served`, flownets/raft.py) is added to the first iteration's coordinates; it is not differentiated."""
     eng = get_engine(net, net0.shape[0], H, W, net0.device)
+    if flow_init is not None:
+        flow_init = flow_init.detach().contiguous()
     from .flownets.raft_corr import AlternateCorrBlock
     if isinstance(corr_fn, AlternateCorrBlock):
         dim = corr_fn._f1.shape[3]
-        return _RaftRefine.apply(net0, inp, eng, True, 1.0 / math.sqrt(dim), corr_fn._f1, *corr_fn._f2)
-    return _RaftRefine.apply(net0, inp, eng, False, 1.0, None, *[v.contiguous() for v in corr_fn.corr_pyramid])
+        return _RaftRefine.apply(net0, inp, eng, True, 1.0 / math.sqrt(dim), flow_init, corr_fn._f1, *corr_fn._f2)
+    return _RaftRefine.apply(net0, inp, eng, False, 1.0, flow_init, None, *[v.contiguous() for v in corr_fn.corr_pyramid])

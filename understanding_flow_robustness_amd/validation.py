@@ -12,6 +12,9 @@ the reference's loop as written, in torch and numpy, on whatever device the item
 
 The datasets are the caller's: every validator takes its loader(s) as a keyword.  Items are what the reference's
 `DataLoader(batch_size=1)` yields: `(image1, image2, flow_gt, valid)`, frames [1,3,H,W] in 0..255, flow_gt [1,2,H,W], valid [1,H,W].
+
+At the end of the file: the test-server submissions of evaluate.py:201-267 (`create_sintel_submission`, `create_kitti_submission`) and
+`forward_interpolate` of models/raft/utils/utils.py:33-59, on the same chunk loop with csrc/submission.hip's two entries.
 """
 from __future__ import annotations
 
@@ -302,3 +305,278 @@ def validate(model, names, loaders, iters: int = 12, flowNetC: bool = False, **k
         elif val_dataset == "kitti":
             results.update(validate_kitti(*head, flowNetC=flowNetC, loader=loaders.get("kitti"), **kwargs))
     return results
+
+
+# ---- the test-server submissions ---------------------------------------------------------------------------------------------------
+# `create_sintel_submission` and `create_kitti_submission` of training/evaluate.py:201-267 with `forward_interpolate` of
+# models/raft/utils/utils.py:33-59, the warm start of the Sintel loop.  The datasets are the caller's here too: the loaders yield the
+# reference's batch-1 items `(image1, image2, (sequence, frame))` / `(image1, image2, (frame_id,))`, plain (`str`, `int`) or as a
+# `DataLoader` collates them (a 1-element list, a 1-element tensor).
+def _interpolate_host(flow, use_scipy=None):
+    """One item [2,h,w] (numpy) on the host, the rule of `ufr_forward_interpolate` (include/ufr_hip.h): with scipy the reference's
+    own arithmetic (`griddata(method="nearest")` over the points that stay inside the grid), otherwise -- `use_scipy=False`, or
+    scipy does not import -- a float64 brute force over chunks of grid pixels in which the lowest index wins a tie."""
+    dx, dy = flow[0], flow[1]
+    ht, wd = dx.shape
+    x0, y0 = np.meshgrid(np.arange(wd), np.arange(ht))
+    x1, y1 = (x0 + dx).reshape(-1), (y0 + dy).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        valid = (x1 > 0) & (x1 < wd) & (y1 > 0) & (y1 < ht)
+    x1, y1, dx, dy = x1[valid], y1[valid], dx.reshape(-1)[valid], dy.reshape(-1)[valid]
+    if x1.size == 0:
+        return np.full((2, ht, wd), np.nan, dtype=np.float32)          # scipy 1.15's answer for an empty point set
+    if use_scipy is None or use_scipy:
+        try:
+            from scipy import interpolate
+        except ImportError:
+            if use_scipy:
+                raise
+            interpolate = None
+        if interpolate is not None:
+            flow_x = interpolate.griddata((x1, y1), dx, (x0, y0), method="nearest", fill_value=0)
+            flow_y = interpolate.griddata((x1, y1), dy, (x0, y0), method="nearest", fill_value=0)
+            return np.stack([flow_x, flow_y], axis=0).astype(np.float32)
+    x1, y1 = x1.astype(np.float64), y1.astype(np.float64)
+    gx, gy = x0.reshape(-1).astype(np.float64), y0.reshape(-1).astype(np.float64)
+    nearest = np.empty(gx.size, dtype=np.int64)
+    step = max(1, (1 << 22) // x1.size)                                 # 32 MiB of distances at a time
+    for s in range(0, gx.size, step):
+        ex, ey = x1[None, :] - gx[s:s + step, None], y1[None, :] - gy[s:s + step, None]
+        nearest[s:s + step] = np.argmin(ex * ex + ey * ey, axis=1)      # (argmin: the first, i.e. lowest, index of a minimum)
+    return np.stack([dx[nearest].reshape(ht, wd), dy[nearest].reshape(ht, wd)], axis=0).astype(np.float32)
+
+
+def forward_interpolate(flow):
+    """models/raft/utils/utils.py:33-59: the flow [2,h,w] (or a batch [B,2,h,w], every item on its own) splatted forward and filled
+    in by nearest neighbour.  A HIP float32 tensor runs `ufr_forward_interpolate` (csrc/submission.hip: exact, one launch, no host
+    synchronisation) and THE RESULT STAYS ON THE INPUT'S DEVICE -- the reference returns a CPU tensor; a caller's `[None].cuda()`
+    works on either.  Any other tensor takes the host restatement (`_interpolate_host`) and comes back as a CPU float32 tensor."""
+    batched = flow.dim() == 4
+    f = flow if batched else flow[None]
+    if f.dim() != 4 or f.shape[1] != 2 or f.shape[0] < 1 or f.shape[2] < 1 or f.shape[3] < 1:
+        raise ValueError(f"forward_interpolate takes a flow of shape [2,h,w] or [B,2,h,w], not {tuple(flow.shape)}")
+    if f.is_cuda and f.dtype == torch.float32:
+        f = f.detach().contiguous()
+        out = torch.empty_like(f)
+        with torch.cuda.device(f.device):
+            L.check(L.lib().ufr_forward_interpolate(L.ptr(f), L.ptr(out), int(f.shape[0]), int(f.shape[2]), int(f.shape[3]), L.stream()),
+                    "forward interpolate")
+    else:
+        out = torch.from_numpy(np.stack([_interpolate_host(item) for item in f.detach().cpu().numpy()])).float()
+    return out if batched else out[0]
+
+
+def _one(value):
+    """An entry of an item's tail, plain or as `DataLoader(batch_size=1)` collates it."""
+    if torch.is_tensor(value):
+        return value.reshape(-1)[0].item()
+    if isinstance(value, (list, tuple)):
+        if len(value) != 1:
+            raise ValueError(f"the loader yields batch-1 items; got {value!r}")
+        return _one(value[0])
+    return value
+
+
+def _sintel_item(item):
+    image1, image2, (sequence, frame) = item
+    return image1, image2, str(_one(sequence)), int(_one(frame))
+
+
+def _kitti_item(item):
+    image1, image2, (frame_id,) = item
+    return image1, image2, str(_one(frame_id))
+
+
+def _require_fused(image1, image2):
+    for t, name in ((image1, "image1"), (image2, "image2")):
+        L.require_hip(t, name, contiguous=False)
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32 (fused=True); fused=False runs the reference's loop on any tensor")
+    check_pair(image1, image2, "the loader yields batch-1 items: image1 and image2 [1,3,H,W]")
+
+
+class _EncodedWriter:
+    """Predictions on their way to disk: `submit` encodes the K padded-frame predictions of a chunk on the device
+    (`ufr_flow_encode`), starts their copy into one of two pinned buffers and THEN writes the files of the previous submit -- the
+    device computes the next chunk meanwhile; `finish` writes the last one.  mode 0: `.flo` files, mode 1: KITTI flow maps."""
+
+    def __init__(self, mode):
+        self.mode, self.item_bytes = mode, (8 if mode == 0 else 6)
+        self.pinned, self.turn, self.pending = [None, None], 0, None
+
+    def submit(self, flow, top, left, H, W, paths):
+        K, Hp, Wp = int(flow.shape[0]), int(flow.shape[2]), int(flow.shape[3])
+        nbytes = K * H * W * self.item_bytes
+        encoded = torch.empty(nbytes, dtype=torch.uint8, device=flow.device)
+        L.check(L.lib().ufr_flow_encode(L.ptr(flow), L.ptr(encoded), K, Hp, Wp, top, left, H, W, self.mode, L.stream()), "flow encode")
+        host = self.pinned[self.turn]
+        if host is None or host.numel() < nbytes:
+            host = self.pinned[self.turn] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.turn ^= 1
+        host[:nbytes].copy_(encoded, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        previous, self.pending = self.pending, (host, nbytes, done, (K, H, W), list(paths))
+        self._write(previous)
+
+    def finish(self):
+        previous, self.pending = self.pending, None
+        self._write(previous)
+
+    def _write(self, job):
+        if job is None:
+            return
+        from . import kitti_io
+        host, nbytes, done, (K, H, W), paths = job
+        done.synchronize()                                             # the one host read of the chunk
+        raw = host.numpy()[:nbytes]
+        if self.mode == 0:
+            for path, flow in zip(paths, raw.view(np.float32).reshape(K, H, W, 2)):
+                kitti_io.write_flo(path, flow)
+        else:
+            for path, codes in zip(paths, raw.view(np.uint16).reshape(K, H, W, 3)):
+                kitti_io.write_flow_kitti(path, codes)
+
+
+class _SubmissionChunks(ChunkedEval):
+    """The chunk's pad, forward, encode and copy; the files are the writer's."""
+
+    def __init__(self, model, iters, pad_mode, writer, chunk, with_flow_init):
+        super().__init__(chunk)
+        self.model, self.iters, self.pad_mode, self.writer, self.with_flow_init = model, iters, pad_mode, writer, with_flow_init
+
+    def add(self, image1, image2, path):
+        _require_fused(image1, image2)
+        super().add((tuple(image1.shape), image1.device), image1, image2, path)
+
+    def padded(self, image1, image2):
+        """Both frames of the stacked pairs on the padded frame (one `ufr_validation_pad`; the frames themselves when nothing is
+        added) and the crop's origin."""
+        K, _, H, W = image1.shape
+        left, right, top, bottom = InputPadder(image1.shape, mode=self.pad_mode)._pad
+        if not (top or bottom or left or right):
+            return image1, image2, 0, 0
+        pad1, pad2 = (torch.empty(K, 3, H + top + bottom, W + left + right, dtype=torch.float32, device=image1.device) for _ in range(2))
+        L.check(L.lib().ufr_validation_pad(L.ptr(image1), L.ptr(image2), L.ptr(pad1), L.ptr(pad2), K, H, W, top, bottom, left, right, 0,
+                                           L.stream()), "validation pad")
+        return pad1, pad2, top, left
+
+    def forward(self, image1, image2, paths, flow_init=None):
+        """pad -> ONE forward -> encode and copy; -> the low-resolution flow."""
+        K, H, W = int(image1.shape[0]), int(image1.shape[2]), int(image1.shape[3])
+        pad1, pad2, top, left = self.padded(image1, image2)
+        self._mark("pad")
+        if self.with_flow_init:
+            flow_low, flow = self.model(pad1, pad2, iters=self.iters, flow_init=flow_init, test_mode=True)
+        else:
+            flow_low, flow = self.model(pad1, pad2, iters=self.iters, test_mode=True)
+        flow = self.checked_flow(flow, K, H, W).to(torch.float32).contiguous()
+        if flow.shape[2] < top + H or flow.shape[3] < left + W:
+            raise RuntimeError(f"the network returned a flow of shape {tuple(flow.shape)} for padded frames of {tuple(pad1.shape)}")
+        self._mark("forward")
+        self.writer.submit(flow, top, left, H, W, paths)
+        self._mark("encode")
+        return flow_low
+
+    def run_chunk(self, items):
+        dev = items[0][1].device
+        image1, image2 = (self.stack_f32([it[i] for it in items], dev) for i in (1, 2))
+        self._mark("start")
+        self.forward(image1, image2, [it[3] for it in items])
+        return ()
+
+    def warm_frame(self, image1, image2, path, flow_low_prev):
+        """One frame of a warm-started chain: interpolate (device) -> pad -> forward -> encode and copy."""
+        _require_fused(image1, image2)
+        with torch.cuda.device(image1.device):
+            self._mark("start")
+            flow_init = None
+            if flow_low_prev is not None:
+                left, right, top, bottom = InputPadder(image1.shape, mode=self.pad_mode)._pad
+                grid = ((int(image1.shape[2]) + top + bottom) // 8, (int(image1.shape[3]) + left + right) // 8)
+                if tuple(flow_low_prev.shape) != (1, 2) + grid:
+                    raise ValueError(f"warm start: the previous frame's low-resolution flow is {tuple(flow_low_prev.shape[2:])}, this "
+                                     f"frame's grid is {grid}: the frames of a sequence must have one size")
+                flow_init = forward_interpolate(flow_low_prev)
+            self._mark("interpolate")
+            return self.forward(image1.detach().contiguous(), image2.detach().contiguous(), [path], flow_init)
+
+
+@torch.no_grad()
+def create_sintel_submission(model, iters: int = 32, warm_start: bool = False, output_path: str = "sintel_submission", *, loaders=None,
+                             chunk: int = 4, fused: bool = True):
+    """Create submission for the Sintel leaderboard (evaluate.py:201-240): per item of `loaders["clean"]` and `loaders["final"]` the
+    pair is padded, `model(image1, image2, iters=iters, flow_init=flow_prev, test_mode=True)` runs, and the unpadded prediction is
+    written to `<output_path>/<dstype>/<sequence>/frame%04d.flo` with `frame + 1`.  With `warm_start` every forward starts from
+    `forward_interpolate` of the previous frame's low-resolution flow; a new sequence starts cold.
+
+    `fused=True` (HIP float32 frames): without `warm_start` up to `chunk` consecutive items of equal size are stacked and per chunk
+    ONE ufr_validation_pad, ONE forward, ONE ufr_flow_encode and one copy to the host run; with `warm_start` the frames of a sequence
+    are a batch-1 chain in which only device launches run between two forwards (interpolate, pad, forward, encode) -- the encoded
+    prediction is copied into a pinned buffer and written to disk while the next frame computes.  `fused=False` is the reference's
+    loop as written, on whatever device the items are on."""
+    _need(loaders, "create_sintel_submission")
+    for dstype in ["clean", "final"]:
+        _need(loaders.get(dstype), f"create_sintel_submission ({dstype})")
+    import os
+
+    from . import kitti_io
+    model.eval()
+    for dstype in ["clean", "final"]:
+        flow_prev, sequence_prev = None, None
+        writer = _EncodedWriter(0)
+        ev = _SubmissionChunks(model, iters, "sintel", writer, 1 if warm_start else chunk, True)
+        ev.events = getattr(create_sintel_submission, "_debug_events", None)   # tools/bench_submission.py: device events per stage
+        for test_data in loaders[dstype]:
+            image1, image2, sequence, frame = _sintel_item(test_data)
+            if sequence != sequence_prev:
+                flow_prev = None
+            output_dir = os.path.join(output_path, dstype, sequence)
+            output_file = os.path.join(output_dir, "frame%04d.flo" % (frame + 1))
+            os.makedirs(output_dir, exist_ok=True)
+            if fused and warm_start:
+                flow_prev = ev.warm_frame(image1, image2, output_file, flow_prev)      # (kept as flow_low: interpolated when it is used)
+            elif fused:
+                ev.add(image1, image2, output_file)
+            else:
+                padder = InputPadder(image1.shape)
+                image1, image2 = padder.pad(image1, image2)
+                flow_low, flow_pr = model(image1, image2, iters=iters, flow_init=flow_prev, test_mode=True)
+                flow = padder.unpad(flow_pr[0]).permute(1, 2, 0).cpu().numpy()
+                if warm_start:
+                    flow_prev = forward_interpolate(flow_low[0])[None].to(image1.device)
+                kitti_io.write_flo(output_file, flow)
+            sequence_prev = sequence
+        ev.read()
+        writer.finish()
+
+
+@torch.no_grad()
+def create_kitti_submission(model, iters: int = 24, output_path: str = "kitti_submission", *, loader=None, chunk: int = 4,
+                            fused: bool = True):
+    """Create submission for the KITTI leaderboard (evaluate.py:243-267): per item `(image1, image2, (frame_id,))` the pair is padded
+    with `mode="kitti"`, `model(image1, image2, iters=iters, test_mode=True)` runs and the unpadded prediction is written as a 16-bit
+    RGB PNG (`kitti_io.write_flow_kitti`) to `os.path.join(output_path, frame_id)`.  `fused` and `chunk` as in
+    `create_sintel_submission`; the codes are then computed on the device (ufr_flow_encode, mode 1)."""
+    _need(loader, "create_kitti_submission")
+    import os
+
+    from . import kitti_io
+    model.eval()
+    os.makedirs(output_path, exist_ok=True)
+    writer = _EncodedWriter(1)
+    ev = _SubmissionChunks(model, iters, "kitti", writer, chunk, False)
+    ev.events = getattr(create_kitti_submission, "_debug_events", None)
+    for test_data in loader:
+        image1, image2, frame_id = _kitti_item(test_data)
+        output_filename = os.path.join(output_path, frame_id)
+        if fused:
+            ev.add(image1, image2, output_filename)
+        else:
+            padder = InputPadder(image1.shape, mode="kitti")
+            image1, image2 = padder.pad(image1, image2)
+            _, flow_pr = model(image1, image2, iters=iters, test_mode=True)
+            flow = padder.unpad(flow_pr[0]).permute(1, 2, 0).cpu().numpy()
+            kitti_io.write_flow_kitti(output_filename, flow)
+    ev.read()
+    writer.finish()

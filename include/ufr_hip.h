@@ -1134,6 +1134,65 @@ int ufr_eval_metrics(const float* pred_clean, const float* pred_adv, const float
                      const float* flow, const int* places, const int* places_host, int K, int H, int W, int Hg, int Wg, int sh,
                      int sw, int ignore_mask_flow, double* ws, long ws_elems, float* out, int row0, int rows, ufr_stream_t stream);
 
+/* ---- flow figures (csrc/flow_viz.hip) -------------------------------------------------------------------------------------------
+ * The Middlebury colour coding of flowutils/flowlib.py:269-306 (`flow_to_image`) and :469-566 (`compute_color`,
+ * `make_color_wheel`), and the six-panel strip `viz###.jpg` of patch_attacks/test_patch.py:467-621 and test_moving_patch.py:529-654.
+ * No entry allocates or synchronises; workspaces come from the caller; maxima only, no float atomics: two runs give the same bytes.
+ * `wheel` is a HOST pointer to the 55 x 3 float64 colour wheel (flowlib.make_color_wheel of the Python package, values 0 .. 255); it
+ * travels by value in the kernel arguments.
+ *
+ * ufr_flow_to_image: flow [K,2,H,W] float32, maxr NULL (the reference's -1) or float32 [K] on the device -> out uint8 [K,H,W,3].
+ *   A pixel with |u| > 1e7 or |v| > 1e7 is unknown: it counts as (0, 0) and gets three zeros.  Launch A: maxrad_k = max sqrt(u*u +
+ *   v*v), float32 with correctly rounded sqrt like the reference's float32 numpy (partials in ws, ufr_flow_to_image_workspace_floats(K)
+ *   floats).  Launch B, float64 in the reference's order: den = (double)max(maxr_k, maxrad_k) + DBL_EPSILON; u / den, v / den; rad =
+ *   sqrt(u*u + v*v); a = atan2(-v, -u) / pi; fk = (a + 1) / 2 * 54 + 1; k0 = floor(fk), k1 = k0 + 1 (56 -> 1), f = fk - k0; per
+ *   channel col = (1 - f) * wheel[k0 - 1] / 255 + f * wheel[k1 - 1] / 255; col = rad <= 1 ? 1 - rad * (1 - col) : col * 0.75; byte =
+ *   floor(255 * col).  A NaN in the flow is outside the contract (the reference casts NaN to uint8, which is undefined): the kernel
+ *   writes 0.  12-byte stores per four pixels when W % 4 == 0, flow is 16-byte and out 4-byte aligned; one pixel per thread otherwise.
+ * ufr_eval_blend_gt: the ground truth that ufr_eval_metrics scores for the attacked prediction, g = (1 - mt) * gt' + mt * f by the
+ *   definitions above (same arguments, same device function: csrc/patch_eval_dev.h), float64 rounded once to float32 [K,3,Hg,Wg]
+ *   (test_patch.py:420-457; the reference blends in float32, so the last bit may differ).
+ * ufr_sweep_blend_gt: the same for the location sweep: position k's g = (1 - m) * gt + m * (0, 0, valid_in_patch) as
+ *   ufr_sweep_metrics scores it (one gt [3,Hg,Wg] for every position, mask_p [3,ph,pw], origins [K,2] on the device and the host),
+ *   float32 [K,3,Hg,Wg] (test_moving_patch.py:414-432).
+ * ufr_viz_ranges: per item the record of UFR_VIZ_RECORD floats that ufr_viz_strip reads, record [K,UFR_VIZ_RECORD] on the device:
+ *   (min, max) of n = (x - 0.5) / 0.5 (float32, custom_transforms.Normalize) over adv_tgt_k, the same of adv_ref_k, maxrad_gt, and
+ *   the own maximum radius of flow_k, adv_flow_k and the float32 difference adv_flow_k - flow_k.  maxrad_gt is the float32 maximum
+ *   radius of the ground-truth panel: g [K,3,Hg,Wg] resized to H x W by cv2.INTER_NEAREST's rule (source index = min(floor(dst *
+ *   ((double)src / dst)), src - 1)), u * (float)(W / Wg), v * (float)(H / Hg) in float32, unknown pixels zeroed (test_patch.py:507-524;
+ *   the script zeroes them in the array it colour codes, so panel 6 shows them white where panels 3-5 show them black).
+ *   The ninth float repeats maxrad_gt: slot 4 is the `maxr` that panels 3-6 are colour coded with, and a caller may replace it
+ *   (flowlib.viz_strip(maxrad_gt=)); slot 8 stays the ground-truth panel's own maximum, so panel 6 normalises by max(slot 4,
+ *   slot 8) as the reference's flow_to_image(val_GT_adv, maxr) does.
+ *   Two launches (partials in ws, ufr_viz_workspace_floats(K) floats; then K workgroups); no host round trip to ufr_viz_strip.
+ * ufr_viz_strip: out uint8 [K,H,6W,3], panels left to right (test_patch.py:592-620):
+ *   1, 2  adv_tgt, adv_ref [K,3,H,W]: n as above; tensor2array's rule (patch_attacks/utils.py:48-53) on the image's own range: n as it
+ *         is when min >= 0 and max <= 1, else 0.5 + 0.5 * n (float32); byte = (uint8)(255 * (double)a), truncated.  A value outside
+ *         0 .. 255 is outside the contract; the kernel saturates.
+ *   3-5   the colour coding above of flow, adv_flow [K,2,H,W] and adv_flow - flow with maxr = maxrad_gt (:532-552);
+ *   6     the ground-truth panel above, colour coded with maxr = slot 4 of the record (its own maximum unless replaced), then a 3 x 3 minimum per channel with positions outside
+ *         the image ignored (cv2.erode's default border, :526-529).
+ *   One launch; 12-byte stores when W % 4 == 0, the four float inputs are 16-byte and out 4-byte aligned, one pixel per thread
+ *   otherwise.
+ * Refused (UFR_EINVAL + ufr_last_error) before any HIP call: null pointers, K < 1, non-positive sizes, a ground truth without its
+ *   sizes (Hg < 1 or Wg < 1), a workspace that is too small, a wheel entry outside 0 .. 255, and for ufr_eval_blend_gt /
+ *   ufr_sweep_blend_gt everything ufr_eval_metrics / ufr_sweep_metrics refuse of the arguments they share. */
+#define UFR_VIZ_RECORD 9
+long ufr_flow_to_image_workspace_floats(int K);   /* -1 when K < 1 */
+int ufr_flow_to_image(const float* flow, const float* maxr, const double* wheel, unsigned char* out, int K, int H, int W, float* ws,
+                      long ws_elems, ufr_stream_t stream);
+int ufr_eval_blend_gt(const float* gt, const float* m_tgt, const float* m_ref, const float* flow, const int* places,
+                      const int* places_host, float* g, int K, int H, int W, int Hg, int Wg, int sh, int sw, int ignore_mask_flow,
+                      ufr_stream_t stream);
+int ufr_sweep_blend_gt(const float* gt, const float* mask_p, const int* origins, const int* origins_host, float* g, int K, int H, int W,
+                       int Hg, int Wg, int ph, int pw, int valid_in_patch, ufr_stream_t stream);
+long ufr_viz_workspace_floats(int K);             /* -1 when K < 1 */
+int ufr_viz_ranges(const float* adv_tgt, const float* adv_ref, const float* flow, const float* adv_flow, const float* g, int K, int H,
+                   int W, int Hg, int Wg, float* ws, long ws_elems, float* record, ufr_stream_t stream);
+int ufr_viz_strip(const float* adv_tgt, const float* adv_ref, const float* flow, const float* adv_flow, const float* g,
+                  const float* record, const double* wheel, unsigned char* out, int K, int H, int W, int Hg, int Wg,
+                  ufr_stream_t stream);
+
 /* ---- global-attack evaluation over a validation set (csrc/global_eval.hip) ------------------------------------------------------
  * global_attacks/perturb_main.py:466-812 runs, per validation item, a clean forward, the attack (or a fixed perturbation) and an
  * attacked forward; global_attacks/log_utils.py:226-528 (`validate`) makes the table from the noises, both predictions and the

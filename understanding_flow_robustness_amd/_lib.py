@@ -310,6 +310,11 @@ SIGNATURES = {
     "ufr_sweep_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
     "ufr_eval_paste": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "ufr_eval_metrics": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
+    "ufr_flow_to_image": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _l, _vp],
+    "ufr_eval_blend_gt": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ufr_sweep_blend_gt": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ufr_viz_ranges": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp],
+    "ufr_viz_strip": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ufr_global_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp],
     "ufr_global_metrics": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _i, _i, _vp],
     "ufr_validation_pad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -339,6 +344,8 @@ PLAIN = {"ufr_abi_version": (C.c_int, []), "ufr_last_error": (C.c_char_p, []),
          "ufr_grad_norm_partials": (C.c_long, [C.POINTER(AdamwSeg), _i]),
          "ufr_sweep_metrics_workspace_doubles": (C.c_long, [_i]),
          "ufr_eval_metrics_workspace_doubles": (C.c_long, [_i]),
+         "ufr_flow_to_image_workspace_floats": (C.c_long, [_i]),
+         "ufr_viz_workspace_floats": (C.c_long, [_i]),
          "ufr_global_metrics_workspace_doubles": (C.c_long, [_i]),
          "ufr_validation_metrics_workspace_doubles": (C.c_long, [_i, _i, _i]),
          "ufr_feature_stats_workspace_doubles": (C.c_long, [C.POINTER(FeatureStatsSeg), _i]),

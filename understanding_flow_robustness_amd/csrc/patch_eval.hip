@@ -9,23 +9,23 @@
 // The reference does, per item: six canvas-sized host arrays and a canvas-sized flow, five H2D copies, ten torch operators for the
 // pastes, two bilinear resizes, a scipy.ndimage.zoom of the canvas flow on the host, ten operators for the blends and four metric
 // calls that each end in `.item()`.
-#include "ufr_common.h"
+#include "patch_eval_dev.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kSlots = ufr::kMetricSlots;
 constexpr int kSums = 6;               // clean: valid * epe, valid * cos, valid; attacked: the same three
-constexpr int kPlace = 8;              // places[k] = {y_tgt, x_tgt, h_tgt, w_tgt, y_ref, x_ref, h_ref, w_ref}
+constexpr int kPlace = ufr::dev::kEvalPlace;
 
 using ufr::aligned16;
-using ufr::dev::Corners;
-using ufr::dev::corners;
 using ufr::dev::epe_cos;
+using ufr::dev::eval_ground_truth;
+using ufr::dev::eval_item;
+using ufr::dev::EvalItem;
 using ufr::dev::FlowTaps;
 using ufr::dev::flow_taps;
 using ufr::dev::paste_clamped;
-using ufr::dev::resized_canvas;
 using ufr::dev::sample;
 
 // idx runs over [K,3,H,W] in units of V floats; the first frame takes record 0 of its item, the second frame record `second`
@@ -97,7 +97,7 @@ __device__ __forceinline__ void pixel_metrics(const double g[3], double fu, doub
 }
 
 // grid (slots, K): workgroup (s, k) walks the ground-truth pixels s * 256 + t, + slots * 256, ... of item k
-// patch_flow: 0 = (0, 0, 0), 1 = (0, 0, 1), 2 = the flow slot; zy / zx: scipy's zoom factors (H - 1) / (Hg - 1), (W - 1) / (Wg - 1)
+// the ground truth of a pixel: patch_eval_dev.h
 __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __restrict__ pred_clean, const float* __restrict__ pred_adv,
                                                               const float* __restrict__ gt, const float* __restrict__ m_tgt,
                                                               const float* __restrict__ m_ref, const float* __restrict__ flow,
@@ -111,60 +111,15 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_kernel(const float* __res
   const float* __restrict__ cv = cu + HW;
   const float* __restrict__ au = pred_adv + (long)k * 2 * HW;
   const float* __restrict__ av = au + HW;
-  const float* __restrict__ gk = gt + (long)k * 3 * HWg;
-  const float* __restrict__ mt = m_tgt + (long)k * 3 * plane;
-  const float* __restrict__ mr = m_ref != nullptr ? m_ref + (long)k * 3 * plane : nullptr;
-  const float* __restrict__ fl = flow != nullptr ? flow + (long)k * 3 * plane : nullptr;
-  const int* __restrict__ pl = places + (long)k * kPlace;
-  const int yt = pl[0], xt = pl[1], ht = pl[2], wt = pl[3];
-  int yr = 0, xr = 0, hr = 0, wr = 0;
-  if (mr != nullptr) { yr = pl[4]; xr = pl[5]; hr = pl[6]; wr = pl[7]; }
+  const EvalItem it = eval_item(gt, m_tgt, m_ref, flow, places, k, HWg, plane);
   const double sy = (double)H / (double)Hg, sx = (double)W / (double)Wg;
   const double scale_u = (double)Wg / (double)W, scale_v = (double)Hg / (double)H;     // losses.py:27
   double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
     const FlowTaps s = flow_taps(p, Wg, sy, sx, H, W);
     const double pu = sample(cu, s), pv = sample(cv, s), qu = sample(au, s), qv = sample(av, s);
-    double g[3] = {(double)gk[p], (double)gk[HWg + p], (double)gk[2 * HWg + p]};
-    if (mr != nullptr) {                                                          // test_patch.py:430-446: occluded by the moved patch
-      const Corners q = corners(s.y0, s.y1, s.x0, s.x1, yr, xr, hr, wr);
-      if (q.any) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) g[c] = (1.0 - resized_canvas(mr + c * plane, sw, q, s.ly, s.lx)) * g[c];
-      }
-    }
-    double ga[3] = {g[0], g[1], g[2]};
-    const Corners q = corners(s.y0, s.y1, s.x0, s.x1, yt, xt, ht, wt);
-    if (q.any) {
-      double f[3] = {0.0, 0.0, patch_flow == 1 ? 1.0 : 0.0};
-      if (patch_flow == 2) {
-        // scipy.ndimage.zoom, order 1, mode='constant' (placement.hip): a source outside [0, n - 1] on either axis gives 0
-        const double cy = zy * (double)s.yg, cx = zx * (double)s.xg;
-        if (!(cy < 0.0 || cy > (double)(H - 1) || cx < 0.0 || cx > (double)(W - 1))) {
-          const int fy0 = (int)floor(cy), fx0 = (int)floor(cx);
-          const double ty = cy - (double)fy0, tx = cx - (double)fx0;
-          const int fy1 = fy0 + 1 < H ? fy0 + 1 : fy0, fx1 = fx0 + 1 < W ? fx0 + 1 : fx0;
-          const double wy1 = fy0 + 1 < H ? ty : 0.0, wx1 = fx0 + 1 < W ? tx : 0.0, wy0 = 1.0 - ty, wx0 = 1.0 - tx;
-          const Corners z = corners(fy0, fy1, fx0, fx1, yt, xt, ht, wt);
-          if (z.any) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-              const float* __restrict__ fc = fl + c * plane;
-              double v = (z.a0 && z.b0 ? (double)fc[z.i0 * sw + z.j0] : 0.0) * (wy0 * wx0);
-              v += (z.a0 && z.b1 ? (double)fc[z.i0 * sw + z.j1] : 0.0) * (wy0 * wx1);
-              v += (z.a1 && z.b0 ? (double)fc[z.i1 * sw + z.j0] : 0.0) * (wy1 * wx0);
-              v += (z.a1 && z.b1 ? (double)fc[z.i1 * sw + z.j1] : 0.0) * (wy1 * wx1);
-              f[c] = v;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const double m = resized_canvas(mt + c * plane, sw, q, s.ly, s.lx);
-        ga[c] = (1.0 - m) * g[c] + m * f[c];                                      // test_patch.py:455-457
-      }
-    }
+    double g[3], ga[3];
+    eval_ground_truth(it, p, HWg, s, H, W, plane, sw, patch_flow, zy, zx, g, ga);
     pixel_metrics(g, pu, pv, scale_u, scale_v, sum);
     pixel_metrics(ga, qu, qv, scale_u, scale_v, sum + 3);
   }
@@ -187,19 +142,6 @@ __global__ __launch_bounds__(kBlock) void eval_metrics_finalize_kernel(const dou
   }
 }
 
-int check_places(const char* what, const int* places_host, int K, int records, int H, int W, int sh, int sw) {
-  for (int k = 0; k < K; ++k)
-    for (int r = 0; r < records; ++r) {
-      const int* p = places_host + (long)k * kPlace + 4 * r;
-      UFR_REQUIRE(p[2] >= 1 && p[2] <= sh && p[3] >= 1 && p[3] <= sw, "%s: item %d, frame %d: the %dx%d record does not fit its %dx%d slot",
-                  what, k, r, p[2], p[3], sh, sw);
-      UFR_REQUIRE(p[0] >= 0 && p[0] <= H - p[2] && p[1] >= 0 && p[1] <= W - p[3],
-                  "%s: item %d, frame %d: placement (%d, %d) of the %dx%d patch leaves the %dx%d frame", what, k, r, p[0], p[1], p[2],
-                  p[3], H, W);
-    }
-  return UFR_OK;
-}
-
 }  // namespace
 
 extern "C" int ufr_eval_paste(const float* tgt, const float* ref, const float* p_tgt, const float* m_tgt, const float* p_ref,
@@ -213,7 +155,7 @@ extern "C" int ufr_eval_paste(const float* tgt, const float* ref, const float* p
   UFR_REQUIRE((long)K * 3 * H * W < (1L << 40) && (long)K * 3 * sh * sw < (1L << 30), "eval paste: too many pixels");
   UFR_REQUIRE(lo <= hi, "eval paste: empty pixel range [%g, %g]", (double)lo, (double)hi);
   const int second = p_ref != nullptr ? 1 : 0;
-  if (int rc = check_places("eval paste", places_host, K, 1 + second, H, W, sh, sw)) return rc;
+  if (int rc = ufr::check_eval_places("eval paste", places_host, K, 1 + second, H, W, sh, sw)) return rc;
   if (!second) { p_ref = p_tgt; m_ref = m_tgt; }
   hipStream_t st = ufr::as_stream(stream);
   const long total = (long)K * 3 * H * W;
@@ -242,7 +184,7 @@ extern "C" int ufr_eval_metrics(const float* pred_clean, const float* pred_adv, 
   UFR_REQUIRE(ignore_mask_flow == 0 || ignore_mask_flow == 1, "eval metrics: ignore_mask_flow = %d (0 or 1)", ignore_mask_flow);
   if (int rc = ufr::check_result_rows("eval metrics", row0, K, rows)) return rc;
   if (int rc = ufr::check_workspace("eval metrics", ws_elems, ufr_eval_metrics_workspace_doubles(K))) return rc;
-  if (int rc = check_places("eval metrics", places_host, K, m_ref != nullptr ? 2 : 1, H, W, sh, sw)) return rc;
+  if (int rc = ufr::check_eval_places("eval metrics", places_host, K, m_ref != nullptr ? 2 : 1, H, W, sh, sw)) return rc;
   hipStream_t st = ufr::as_stream(stream);
   const int slots = ufr::metric_slots((long)Hg * Wg, kBlock);
   const int patch_flow = flow != nullptr ? 2 : (ignore_mask_flow ? 0 : 1);

@@ -9,7 +9,7 @@
 // resize of the mask, five for the blend, two metric calls that each end in `.item()`.
 #include <climits>
 
-#include "ufr_common.h"
+#include "patch_eval_dev.h"
 
 namespace {
 
@@ -162,13 +162,11 @@ __global__ __launch_bounds__(kBlock) void sweep_paste_window_kernel(const float*
 }
 
 // ---- metrics ------------------------------------------------------------------------------------------------------------------
-using ufr::dev::Corners;            // the canvas mask at the prediction's taps
-using ufr::dev::corners;
 using ufr::dev::epe_cos;
 using ufr::dev::FlowTaps;           // torch's upsample_bilinear2d, align_corners = False, in float64
 using ufr::dev::flow_taps;
-using ufr::dev::resized_canvas;
 using ufr::dev::sample;
+using ufr::dev::sweep_ground_truth;  // the canvas mask at the prediction's taps, the blend (patch_eval_dev.h)
 
 // grid (slots, K): workgroup (s, k) walks the ground-truth pixels s * 256 + t, + slots * 256, ... of position k
 __global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -188,18 +186,8 @@ __global__ __launch_bounds__(kBlock) void sweep_metrics_kernel(const float* __re
   for (long p = (long)blockIdx.x * kBlock + threadIdx.x; p < HWg; p += (long)gridDim.x * kBlock) {
     const FlowTaps s = flow_taps(p, Wg, sy, sx, H, W);
     const double fu = sample(pu, s), fv = sample(pv, s);
-    double g[3] = {(double)gt[p], (double)gt[HWg + p], (double)gt[2 * HWg + p]};
-    if (mask_p != nullptr) {
-      // the canvas mask at the (already clamped) source rows / columns: mask_p inside the rectangle, 0 outside
-      const Corners q = corners(s.y0, s.y1, s.x0, s.x1, oy, ox, ph, pw);
-      if (q.any) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const double m = resized_canvas(mask_p + (long)c * ph * pw, pw, q, s.ly, s.lx);
-          g[c] = (1.0 - m) * g[c] + m * (c == 2 ? patch_valid : 0.0);            // test_moving_patch.py:430-432
-        }
-      }
-    }
+    double g[3];
+    sweep_ground_truth(gt, p, HWg, mask_p, oy, ox, ph, pw, patch_valid, s, g);       // test_moving_patch.py:430-432
     double epe, cs;                                                               // losses.py:29-30: the error against the rescaled
     epe_cos(g[0] - fu * scale_u, g[1] - fv * scale_v, g[0], g[1], fu, fv, epe, cs);  // prediction, the cosine with it as it is
     sum[0] += epe * g[2];
@@ -223,15 +211,6 @@ __global__ __launch_bounds__(kBlock) void sweep_metrics_finalize_kernel(const do
   }
 }
 
-int check_origins(const char* what, const int* origins_host, int K, int H, int W, int ph, int pw) {
-  for (int k = 0; k < K; ++k)
-    UFR_REQUIRE(origins_host[2 * k] >= 0 && origins_host[2 * k] + ph <= H && origins_host[2 * k + 1] >= 0 &&
-                    origins_host[2 * k + 1] + pw <= W,
-                "%s: placement %d = (%d, %d) of the %dx%d patch leaves the %dx%d frame", what, k, origins_host[2 * k],
-                origins_host[2 * k + 1], ph, pw, H, W);
-  return UFR_OK;
-}
-
 }  // namespace
 
 extern "C" int ufr_sweep_paste(const float* tgt, const float* ref, const float* patch_p, const float* mask_p, const int* origins,
@@ -243,7 +222,7 @@ extern "C" int ufr_sweep_paste(const float* tgt, const float* ref, const float* 
   UFR_REQUIRE(ph <= H && pw <= W, "sweep paste: the %dx%d patch is larger than the %dx%d frame", ph, pw, H, W);
   UFR_REQUIRE((long)K * 3 * H * W < (1L << 40) && (long)3 * ph * pw < (1L << 30), "sweep paste: too many pixels");
   UFR_REQUIRE(lo <= hi, "sweep paste: empty pixel range [%g, %g]", (double)lo, (double)hi);
-  if (int rc = check_origins("sweep paste", origins_host, K, H, W, ph, pw)) return rc;
+  if (int rc = ufr::check_sweep_origins("sweep paste", origins_host, K, H, W, ph, pw)) return rc;
   hipStream_t st = ufr::as_stream(stream);
   if (win == nullptr) {
     UFR_REQUIRE(chain == nullptr && xw == nullptr, "sweep paste: a chain or window stack without the window table");
@@ -303,7 +282,7 @@ extern "C" int ufr_sweep_metrics(const float* pred, const float* gt, const float
     UFR_REQUIRE(ph > 0 && pw > 0, "sweep metrics: bad shape ph=%d pw=%d", ph, pw);
     UFR_REQUIRE(ph <= H && pw <= W && (long)3 * ph * pw < (1L << 30), "sweep metrics: the %dx%d patch is larger than the %dx%d frame",
                 ph, pw, H, W);
-    if (int rc = check_origins("sweep metrics", origins_host, K, H, W, ph, pw)) return rc;
+    if (int rc = ufr::check_sweep_origins("sweep metrics", origins_host, K, H, W, ph, pw)) return rc;
   }
   hipStream_t st = ufr::as_stream(stream);
   const int slots = ufr::metric_slots((long)Hg * Wg, kBlock);

@@ -13,10 +13,17 @@ consecutive items of equal size are stacked, and per chunk
     ufr_eval_paste (csrc/patch_eval.hip)  ->  ONE forward of the 2K clean and pasted pairs  ->  ufr_eval_metrics
 
 run; the host reads the results once, at the end.
+
+With `save_path` the script's outputs are produced too (test_patch.py:163-236, :467-643): per chunk `ufr_eval_blend_gt` writes the
+ground truth that was scored, `flowlib.viz_strip` (csrc/flow_viz.hip) builds the six-panel strips on the device, ONE copy takes them
+into one of two pinned buffers and the files of the previous chunk are written while the device computes (the pattern of
+validation._EncodedWriter); the CSV files follow at the end.  TensorBoard stays with the caller.
 """
 from __future__ import annotations
 
 from argparse import Namespace
+import os
+import warnings
 from dataclasses import dataclass
 
 import numpy as np
@@ -32,6 +39,99 @@ class EvalResult:
     mean: np.ndarray             # float64 [4]: the plain mean over items (what the script's AverageMeter reports)
     locations: list              # per item [(x_tgt, y_tgt), (x_ref, y_ref)]
     error_names: list
+
+    def csv_text(self):
+        """(test_results.csv, test_result_scenes.csv) as the script writes them (test_patch.py:229-236, :623-643): the header, in
+        the scene file one line per item, and the average as its AverageMeter forms it (a running sum in item order over the
+        count)."""
+        names = list(self.error_names)
+        results = "{:>10}, {:>10}, {:>10}, {:>10}\n".format(*names)
+        scenes = "{:>10}, {:>10}, {:>10}, {:>10}, {:>10}\n".format(*(["scene"] + names))
+        total = [0.0] * 4
+        for i, row in enumerate(self.per_item):
+            row = [float(v) for v in row]
+            total = [t + v for t, v in zip(total, row)]
+            scenes += "{:10d}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}\n".format(i, *row)
+        avg = [t / len(self.per_item) for t in total] if len(self.per_item) else [0] * 4
+        results += "{:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}\n".format(*avg)
+        scenes += "{:>10}, {:10.4f}, {:10.4f}, {:10.4f}, {:10.4f}\n".format(*(["avg"] + avg))
+        return results, scenes
+
+    def write_csv(self, save_path, different_pos=False):
+        """`test_results[_diff_pos].csv` and `test_result_scenes[_diff_pos].csv` under `save_path` (test_patch.py:203-215); -> the
+        two paths."""
+        os.makedirs(save_path, exist_ok=True)
+        tail = "_diff_pos.csv" if different_pos else ".csv"
+        paths = os.path.join(save_path, "test_results" + tail), os.path.join(save_path, "test_result_scenes" + tail)
+        for path, text in zip(paths, self.csv_text()):
+            with open(path, "w", encoding="utf-8") as f:
+                f.write(text)
+        return paths
+
+
+IMAGE_FORMATS = ("jpg", "png")
+
+
+def save_strip(path, strip, image_format):
+    """One strip, uint8 [H,6W,3] -> `path`: "jpg" as the script saves it (PIL's defaults), "png" lossless through
+    `kitti_io.png_write`."""
+    if image_format == "jpg":
+        from PIL import Image
+        Image.fromarray(strip).save(path)
+    else:
+        from . import kitti_io
+        kitti_io.png_write(path, strip)
+
+
+def checked_image_format(image_format):
+    """"jpg" needs PIL; without it the strips are written as png, with a warning."""
+    if image_format not in IMAGE_FORMATS:
+        raise ValueError(f"image_format must be one of {IMAGE_FORMATS}, not {image_format!r}")
+    if image_format == "jpg":
+        try:
+            import PIL.Image  # noqa: F401
+        except ImportError:
+            warnings.warn("PIL is not installed: the strips are written as viz###.png (lossless) instead of viz###.jpg")
+            return "png"
+    return image_format
+
+
+class StripWriter:
+    """Strips on their way to disk: `submit` starts the ONE copy of a chunk's strips into one of two pinned buffers and THEN writes
+    the files of the previous submit -- the device computes meanwhile; `finish` writes the last one."""
+
+    def __init__(self, directory, image_format):
+        self.directory, self.format = directory, checked_image_format(image_format)
+        os.makedirs(directory, exist_ok=True)
+        self.pinned, self.turn, self.pending, self.paths = [None, None], 0, None, []
+
+    def path(self, index):
+        return os.path.join(self.directory, "viz" + str(index).zfill(3) + "." + self.format)
+
+    def submit(self, strips, first_index):
+        host = self.pinned[self.turn]
+        if host is None or host.numel() < strips.numel():
+            host = self.pinned[self.turn] = torch.empty(strips.numel(), dtype=torch.uint8).pin_memory()
+        self.turn ^= 1
+        host[:strips.numel()].copy_(strips.reshape(-1), non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        previous, self.pending = self.pending, (host, tuple(strips.shape), done, first_index)
+        self._write(previous)
+
+    def finish(self):
+        previous, self.pending = self.pending, None
+        self._write(previous)
+
+    def _write(self, job):
+        if job is None:
+            return
+        host, shape, done, first_index = job
+        done.synchronize()                                             # the one host read of the chunk
+        strips = host.numpy()[:int(np.prod(shape))].reshape(shape)
+        for k, strip in enumerate(strips):
+            self.paths.append(self.path(first_index + k))
+            save_strip(self.paths[-1], strip, self.format)
 
 
 def _refuse_3d(what):
@@ -57,6 +157,8 @@ class _Evaluation(ChunkedEval):
         self.square = getattr(args, "patch_type", "circle") == "square"
         self.fixed_loc = (int(getattr(args, "fixed_loc_x", -1)), int(getattr(args, "fixed_loc_y", -1)))
         self.locations = []
+        self.writer, self.done = None, 0                         # StripWriter of a call with save_path; items run so far
+        self.figure_hook = None                                  # the tests: what the strips of a chunk were built from
 
     def _state(self, dev):
         if self.patch_d is None:
@@ -119,6 +221,17 @@ class _Evaluation(ChunkedEval):
                                      places_host.ctypes.data, K, H, W, Hg, Wg, slot, slot, self.ignore, L.ptr(ws), ws.numel(),
                                      L.ptr(out), 0, K, L.stream()), "eval metrics")
         self._mark("metrics")
+        if self.writer is not None:
+            from . import flowlib
+            g = torch.empty(K, 3, Hg, Wg, dtype=torch.float32, device=dev)
+            L.check(lib.ufr_eval_blend_gt(L.ptr(gt), L.ptr(m_tgt), opt(m_ref), opt(flow), L.ptr(places), places_host.ctypes.data,
+                                          L.ptr(g), K, H, W, Hg, Wg, slot, slot, self.ignore, L.stream()), "eval blend gt")
+            self._mark("blend")
+            if self.figure_hook is not None:
+                self.figure_hook(self.done, adv_tgt, adv_ref, flows[:K], flows[K:], g)
+            strips = flowlib.viz_strip(adv_tgt, adv_ref, flows[:K], flows[K:], g, events=self._mark if self.events is not None else None)
+            self.writer.submit(strips, self.done)
+        self.done += K
         return out
 
     def write_back(self):
@@ -132,8 +245,25 @@ class _Evaluation(ChunkedEval):
                 np.copyto(dst, src.cpu().numpy().astype(dst.dtype, copy=False))
 
 
-def evaluate_patch(flow_net, val_loader, patch, mask, patch_shape, args: Namespace, chunk=4) -> EvalResult:
-    """test_patch.py:242-466 without its images, CSV files and TensorBoard.
+def output_dirs(save_path, args):
+    """test_patch.py:163-177, :203-215: (where the CSV files go, where the images go)."""
+    save_path = os.fspath(save_path)
+    if getattr(args, "HOMOGENUOUS", False):
+        save_path = os.path.join(save_path, "homogenuous_img")
+        return save_path, save_path
+    return save_path, os.path.join(save_path, "images_test_diff_pos" if getattr(args, "different_pos", False) else "images_test")
+
+
+def evaluate_patch(flow_net, val_loader, patch, mask, patch_shape, args: Namespace, chunk=4, save_path=None,
+                   image_format="jpg") -> EvalResult:
+    """test_patch.py:242-643 without TensorBoard; with `save_path=None` without its images and CSV files too, and then the call
+    launches nothing else.
+
+    save_path: the script's `args.save_path`.  Per item the six-panel strip `images_test/viz%03d.jpg` (`images_test_diff_pos/`
+    with different_pos; with HOMOGENUOUS everything goes into `save_path/homogenuous_img`), saved with PIL's defaults like the
+    script's; `image_format="png"` writes `viz%03d.png` losslessly (also what is written, with a warning, when PIL is missing).
+    `test_results[_diff_pos].csv` and `test_result_scenes[_diff_pos].csv` get the script's lines (`EvalResult.write_csv` writes them
+    alone).  A network that answers below frame size (the script's `zoom` for FlowNetS) is refused.
 
     val_loader yields the reference's batch-1 items `(ref_past, tgt, ref, flow_gt[, disp_gt, calib, poses])` as HIP tensors
     (frames [1,3,H,W], flow_gt [1,3,Hg,Wg] = (u, v, valid)); patch / mask: [1,3,S,S] numpy arrays or tensors, as
@@ -151,6 +281,10 @@ def evaluate_patch(flow_net, val_loader, patch, mask, patch_shape, args: Namespa
     if len(patch.shape) != 4 or tuple(patch.shape[:2]) != (1, 3) or tuple(mask.shape) != tuple(patch.shape):
         raise ValueError("patch and mask must be [1,3,S,S], in patch coordinates")
     ev.events = getattr(evaluate_patch, "_debug_events", None)            # tools/bench_patch_eval.py: device events around the entries
+    if save_path is not None:
+        csv_dir, image_dir = output_dirs(save_path, args)
+        ev.writer = StripWriter(image_dir, image_format)
+        ev.figure_hook = getattr(evaluate_patch, "_debug_figures", None)
     with torch.no_grad():
         for item in val_loader:
             tgt, ref, gt = item[1], item[2], item[3]
@@ -171,7 +305,12 @@ def evaluate_patch(flow_net, val_loader, patch, mask, patch_shape, args: Namespa
             ev.add(tgt, ref, gt, rec)
         ev.flush()
         ev.write_back()
+        if ev.writer is not None:
+            ev.writer.finish()
         rows = ev.read()                                                              # the one host synchronisation of the call
         per_item = rows[0].astype(np.float64) if rows else np.zeros((0, 4))
     mean = per_item.mean(axis=0) if len(per_item) else np.zeros(4)
-    return EvalResult(per_item, mean, ev.locations, list(ERROR_NAMES))
+    result = EvalResult(per_item, mean, ev.locations, list(ERROR_NAMES))
+    if save_path is not None:
+        result.write_csv(csv_dir, ev.different)
+    return result

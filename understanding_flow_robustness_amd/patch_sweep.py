@@ -15,10 +15,15 @@ windowed  networks with a convolutional prefix on the native FlowNetC engine (co
           frames never change and only the window moves, so conv1-3 of the clean pair are computed once, every chunk restores them
           (`load_prefix_features`), runs the prefix on a window around each position's patch (`window_prefix_forward`) and the head
           at full size (`forward_cached`).  The canvases are never materialised.
+
+`sweep_scenes` is the scene loop of test_moving_patch.py:246-678 around it: per scene the statistics of both maps, the map resized
+to the frame (`adv_epe_image_%03d.npy`), one more paste and forward at the first worst position and its six-panel strip
+(flowlib.viz_strip on the ground truth `ufr_sweep_blend_gt` writes), and the script's two CSV files.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from argparse import Namespace
 from dataclasses import dataclass
 
@@ -254,3 +259,158 @@ def sweep_patch_locations(flow_net, tgt_img, ref_future_img, flow_gt, patch, mas
         if out[i, 0] > worst_epe:                                  # strict: the first maximum (test_moving_patch.py:447)
             worst_epe, worst = out[i, 0], (y, x)
     return SweepResult(adv_epe, adv_cos, float(out[-1, 0]), float(out[-1, 1]), worst, locations, bool(windowed))
+
+
+# ---- the scene loop --------------------------------------------------------------------------------------------------------------------
+RESULT_NAMES = ["epe", "adv_epe_avg", "adv_epe_min", "adv_epe_median", "adv_epe_max", "cos_sim", "adv_cos_sim_avg", "adv_cos_min",
+                "adv_cos_median", "adv_cos_max"]                       # test_moving_patch.py:226-237
+
+
+def moving_headers():
+    """(header of moving_results.csv, header of moving_result_scenes.csv), test_moving_patch.py:238-245."""
+    names = ", ".join(RESULT_NAMES) + "\n"
+    return names, "scene, " + names
+
+
+def _rounded_row(values):
+    """The script's f-string of ten `round(., 4)` (test_moving_patch.py:503, :674): no blank after the first comma."""
+    r = [round(v, 4) for v in values]
+    return f"{r[0]},{r[1]}, " + ", ".join(str(v) for v in r[2:]) + "\n"
+
+
+def moving_scene_line(index, values):
+    return f"{index}, " + _rounded_row(values)
+
+
+def moving_total_line(values):
+    return _rounded_row(values)
+
+
+class _Meter:
+    """The script's AverageMeter (patch_attacks/logger.py:83-109) for one quantity: a running sum over the count, the minimum
+    starting at 10e6 and the maximum starting at 0 -- so a map without a positive value reports a maximum of 0, like the script."""
+
+    def __init__(self):
+        self.sum, self.count, self.min, self.max = 0, 0, 10e6, 0
+
+    def update(self, v):
+        self.count += 1
+        self.sum += v
+        self.min = v if v < self.min else self.min
+        self.max = v if v > self.max else self.max
+
+    @property
+    def avg(self):
+        return self.sum / self.count
+
+
+def scene_statistics(adv_epe, adv_cos_sim):
+    """avg, min, median and max of both maps [ny, nx] as test_moving_patch.py:490-500 forms them: the meter over the positions in
+    visiting order (x outer, y inner), the median by numpy."""
+    stats = {}
+    for name, m in (("adv_epe", np.asarray(adv_epe)), ("adv_cos_sim", np.asarray(adv_cos_sim))):
+        meter, values = _Meter(), [float(v) for v in m.T.reshape(-1)]
+        for v in values:
+            meter.update(v)
+        stats[name + "_avg"], stats[name + "_min"], stats[name + "_max"] = meter.avg, meter.min, meter.max
+        stats[name + "_median"] = float(np.median(values))
+    return stats
+
+
+def zoomed_map(adv_epe, H, W):
+    """test_moving_patch.py:474-481: the map resized to the frame by scipy.ndimage.zoom, order 1."""
+    from scipy.ndimage import zoom
+    adv_epe = np.asarray(adv_epe)
+    return zoom(adv_epe, zoom=(H / adv_epe.shape[-2], W / adv_epe.shape[-1]), order=1)
+
+
+def worst_strip(flow_net, tgt, ref, flow_gt, patch, mask, args, worst, ignore_mask_flow=False):
+    """test_moving_patch.py:447-471, :529-654: one paste and one forward of the clean and the pasted pair at position `worst` =
+    (y, x), the ground truth that position was scored with, and the six-panel strip: uint8 HIP tensor [1,H,6W,3]."""
+    from . import flowlib
+    from .flownets.utils_model import predict_flow
+    from .patch_attack import _pixel_range
+    dev = tgt.device
+    with torch.no_grad(), torch.cuda.device(dev):
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        tgt, ref, gt = f32(tgt), f32(ref), f32(flow_gt)
+        patch_p, mask_p = _placed_patch(patch, mask, dev)
+        H, W, Hg, Wg = int(tgt.shape[2]), int(tgt.shape[3]), int(gt.shape[2]), int(gt.shape[3])
+        ph, pw = int(patch_p.shape[2]), int(patch_p.shape[3])
+        lo, hi = _pixel_range(args.flownet)
+        origin_host = np.ascontiguousarray(np.asarray([worst], dtype=np.int32).reshape(1, 2))
+        origin = torch.from_numpy(origin_host).to(dev)
+        adv_tgt, adv_ref = torch.empty_like(tgt), torch.empty_like(ref)
+        lib = L.lib()
+        L.check(lib.ufr_sweep_paste(L.ptr(tgt), L.ptr(ref), L.ptr(patch_p), L.ptr(mask_p), L.ptr(origin), origin_host.ctypes.data,
+                                    L.ptr(adv_tgt), L.ptr(adv_ref), 1, H, W, ph, pw, lo, hi, None, 0, 0, None, None, L.stream()),
+                "sweep paste")
+        flows = predict_flow(flow_net, None, torch.cat((tgt, adv_tgt)), torch.cat((ref, adv_ref)), args).contiguous()
+        g = torch.empty(1, 3, Hg, Wg, dtype=torch.float32, device=dev)
+        L.check(lib.ufr_sweep_blend_gt(L.ptr(gt), L.ptr(mask_p), L.ptr(origin), origin_host.ctypes.data, L.ptr(g), 1, H, W, Hg, Wg, ph,
+                                       pw, 0 if ignore_mask_flow else 1, L.stream()), "sweep blend gt")
+        hook = getattr(worst_strip, "_debug_figures", None)            # the tests: what the strip was built from
+        if hook is not None:
+            hook(tuple(worst), adv_tgt, adv_ref, flows[:1], flows[1:], g)
+        return flowlib.viz_strip(adv_tgt, adv_ref, flows[:1], flows[1:], g)
+
+
+def sweep_scenes(flow_net, loader, patch, mask, args: Namespace, stride=25, chunk=8, save_path=None, image_format="jpg",
+                 ignore_mask_flow=False, cone=None):
+    """The scene loop of test_moving_patch.py:246-678 around `sweep_patch_locations`, under its preconditions (`--norotate`, no
+    calibration: an item with calibration needs the 3-D projection and raises NotImplementedError).
+
+    loader yields the reference's batch-1 items `(ref_past, tgt, ref, flow_gt[, disp_gt, calib, poses])` as HIP tensors.  Per scene:
+    the sweep and the clean metrics, the statistics of `scene_statistics`, and -- with `save_path` -- `viz%03d.jpg` in
+    `save_path/moving_patch_worst_images` (the strip at the first worst position; `image_format="png"` lossless),
+    `adv_epe_image_%03d.npy` in `save_path/moving_patch` (the map resized to the frame; the matplotlib overlay the script draws from
+    it stays with the caller) and a row of `moving_result_scenes.csv`; at the end the one row of `moving_results.csv`.
+
+    Returns (the per-scene SweepResults, table): table["scenes"] = per scene the ten numbers of `RESULT_NAMES`, table["total"] the
+    ten of `moving_results.csv`: the running averages over ALL positions of all scenes and the means of the scenes' minima, medians
+    and maxima (:660-675)."""
+    from .patch_eval import StripWriter
+    results, scenes = [], []
+    totals = [_Meter() for _ in range(4)]                               # epe, adv_epe, cos_sim, adv_cos over every position
+    writer = map_dir = None
+    if save_path is not None:
+        save_path = os.fspath(save_path)
+        map_dir = os.path.join(save_path, "moving_patch")
+        os.makedirs(map_dir, exist_ok=True)
+        writer = StripWriter(os.path.join(save_path, "moving_patch_worst_images"), image_format)
+        header, scene_header = moving_headers()
+        with open(os.path.join(save_path, "moving_results.csv"), "w", encoding="utf-8") as f:
+            f.write(header)
+        with open(os.path.join(save_path, "moving_result_scenes.csv"), "w", encoding="utf-8") as f:
+            f.write(scene_header)
+    for i, item in enumerate(loader):
+        tgt, ref, gt = item[1], item[2], item[3]
+        if len(item) > 5 and len(item[5]) > 0:
+            raise NotImplementedError("an item with calibration: the reference projects the patch into the 3-D scene "
+                                      "(project_patch_3d_scene); that projection is not part of this project")
+        r = sweep_patch_locations(flow_net, tgt, ref, gt, patch, mask, args, stride=stride, chunk=chunk,
+                                  ignore_mask_flow=ignore_mask_flow, cone=cone)
+        results.append(r)
+        for y, x in r.locations:                                        # errors.update per position, in visiting order (:438)
+            for meter, v in zip(totals, (r.epe, r.adv_epe[y // stride, x // stride], r.cos_sim, r.adv_cos_sim[y // stride, x // stride])):
+                meter.update(float(v))
+        st = scene_statistics(r.adv_epe, r.adv_cos_sim)
+        scenes.append([r.epe, st["adv_epe_avg"], st["adv_epe_min"], st["adv_epe_median"], st["adv_epe_max"], r.cos_sim,
+                       st["adv_cos_sim_avg"], st["adv_cos_sim_min"], st["adv_cos_sim_median"], st["adv_cos_sim_max"]])
+        if save_path is not None:
+            strip = worst_strip(flow_net, tgt, ref, gt, patch, mask, args, r.worst, ignore_mask_flow)
+            writer.submit(strip, i)                                     # written while the next scene's sweep runs
+            np.save(os.path.join(map_dir, "adv_epe_image_" + str(i).zfill(3) + ".npy"),
+                    zoomed_map(r.adv_epe, int(tgt.shape[-2]), int(tgt.shape[-1])))
+            with open(os.path.join(save_path, "moving_result_scenes.csv"), "a", encoding="utf-8") as f:
+                f.write(moving_scene_line(i, scenes[-1]))
+    if writer is not None:
+        writer.finish()
+    table = {"names": list(RESULT_NAMES), "scenes": np.asarray(scenes, dtype=np.float64).reshape(-1, 10), "total": None}
+    if scenes:
+        col = lambda j: float(np.mean([s[j] for s in scenes]))
+        table["total"] = [totals[0].avg, totals[1].avg, col(2), col(3), col(4), totals[2].avg, totals[3].avg, col(7), col(8), col(9)]
+        if save_path is not None:
+            with open(os.path.join(save_path, "moving_results.csv"), "a", encoding="utf-8") as f:
+                f.write(moving_total_line(table["total"]))
+    return results, table
